@@ -7,16 +7,31 @@ batches (BASELINE.json metric), one process per GPU.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W [--batch 8] [--variant mma --p-drop 0.4]
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's headline needs: set-up,
+W warm-up steps, K timed steps (every one of them the production step), --dump-outputs if given, the line.  `ms_per_step` is the
+wall time of the K timed steps / K, and `config.launch_choice` says what --launch auto chose and why (the two-step
+replay-vs-eager guard under data parallelism).
+
+--full adds everything else the benchmark measures, as extra objects of the same line:
   roofline     : the dominant kernel of the step, timed live with HIP events on its launch stream; achieved =
-                 algorithmic flops per launch / average launch duration (DESIGN.md section "Measurement").
+                 algorithmic flops per launch / average launch duration (DESIGN.md section "Measurement"); `kernels`: every
+                 timed entry point (every --sample-every-th timed step runs eagerly with HIP events around each launch;
+                 --no-kernel-timing: off).
   cpu_baseline : the oracle (CPU restatement of the reference, oracle/mca_oracle.py) timed on this host on a
-                 bounded sample of the same workload (N=1, rank 0 only).
-and, inside `config`: launch_choice (what --launch auto chose and why; the two-step replay-vs-eager guard under data parallelism),
-gpu_state_rank0 (shader clock / board power over the timed region, sysfs) and - single GPU, replayed step - sustained: the rate of
-the same replayed step after 30 s of unbroken load, measured AFTER the timed region and never used for `value` (every process
-starts in the slower of the chip's two sustained-load operating points, profiles/r04_slow_regime.md; --sustain-seconds 0: off).
---step-times prints the host clock after every timed step (the sampled step's cost is visible there).
+                 bounded sample of the same workload (N=1, rank 0 only; --no-cpu-baseline: off).
+and, inside `config`: gpu_state_rank0 (shader clock / board power over the timed region, sysfs) and - single GPU, replayed step -
+sustained: the rate of the same replayed step after 30 s of unbroken load, measured AFTER the timed region and never used for
+`value` (every process starts in the slower of the chip's two sustained-load operating points, profiles/r04_slow_regime.md;
+--sustain-seconds 0: off).
+--step-times prints the host clock after every timed step (with --full the sampled step's cost is visible there).
+--dump-outputs DIR writes what the last timed step computed (rank 0), float32, as DIR/<name>.npy: loss (0-d), loss_terms (the
+loss terms in the model's order), pooled (batch x output slots x D, the forward's pooled embeddings), and a fixed seeded sample
+(the same indices on every run of the same workload) of the flat fp32 weights after the optimizer step (weights_sample) and of
+the step's unscaled gradients (grads_sample).  Inputs and initial weights are seeded: two builds run with the same arguments
+can be compared output for output: the last timed step starts from the seeded weights and optimizer state (see
+restore_seeded_state), so what it computes is the same in every run up to the rounding of that one step (the order of the fp32
+atomics of the weight-gradient splits; without the reset, AdamW carries those last bits from step to step and two runs of
+3 + 20 steps at b = 32 differed by ~2 % in the loss).
 The step timed is the one train_accel_gpu.py runs: finite checks ON (device flag, polled without a host sync; the
 fused AdamW skips a flagged step), inputs resident in HBM (same batch every step).
 """
@@ -148,6 +163,41 @@ def host_cpu():
     return model, max(1, n)
 
 
+DUMP_SAMPLE = 1 << 21          # elements of each seeded sample written by --dump-outputs (8 MB in float32)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, model, out) -> None:
+    """--dump-outputs (module docstring): the last timed step's outputs as float32 DIR/<name>.npy.  The flat weight and gradient
+    buffers are sampled at DUMP_SAMPLE indices drawn from a fixed seed; `pooled` is sampled the same way only when it is larger
+    than that (a batch far above the default)."""
+    import numpy as np
+    eng = model.engine
+    by_slot = {}
+    for k, s in model.output_slots().items():
+        by_slot.setdefault(s, k)
+
+    drawn = {}
+
+    def sample(x):          # (weights and gradients: the same indices)
+        if x.numel() <= DUMP_SAMPLE:
+            return x
+        if x.numel() not in drawn:
+            drawn[x.numel()] = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values.to(x.device)
+        return x.reshape(-1)[drawn[x.numel()]]
+    arrays = {"loss": out["loss"].reshape(()),
+              "loss_terms": torch.stack([v.reshape(()) for v in out["losses"].values()]),
+              "pooled": sample(torch.stack([out[by_slot[s]] for s in sorted(by_slot)], 1)),
+              "weights_sample": sample(eng.flat),
+              "grads_sample": sample(eng.gflat)}
+    arrays = {k: v.detach().float().contiguous().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def cpu_baseline(P, workload: str, variant: str, protocol: str):
     """the oracle's full step (fwd + bwd + clip + AdamW), fp32, b = 8, the same synthetic CMU-shaped
     batch generator (count of threads and CPU model stated).  protocol 'short' (default, keeps the bench within minutes):
@@ -216,7 +266,11 @@ def main():
     ap.add_argument("--step-times", action="store_true", help="print the host clock after every timed step to stderr (diagnosis)")
     ap.add_argument("--launch", default="auto", choices=["auto", "eager", "graph"], help="auto: hipGraph replay (one graph on one GPU; graph segments cut at the eager collectives under data parallelism); falls back to the eager loop if the capture fails")
     ap.add_argument("--sample-every", type=int, default=20, help="record per-kernel HIP events on every n-th timed step (a sampled step runs its kernels one at a time and costs ~1.3 steps)")
+    ap.add_argument("--full", action="store_true", help="also the figures beyond the headline: roofline / per-kernel timing, cpu_baseline, gpu_state_rank0 and sustained")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one computed as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -258,6 +312,18 @@ def main():
     dp = dpmod.DataParallelMCA(model) if world > 1 else None
     batch = P.data.synthetic_batch(cfg, b, seed=1234 + rank, p_drop=args.p_drop, lengths=args.lengths, device=dev)
 
+    # The seeded state (weights, AdamW moments, step count) before the first step.  The fp32 atomics of the weight-gradient
+    # splits make every step's gradients differ from run to run in the last bits, and AdamW carries that into the weights from
+    # step to step, so after W + K steps two runs no longer start their last step from the same weights.  The last timed step
+    # therefore starts from this state again (three device copies, ~0.1 ms once): what it computes depends on the arguments
+    # alone, up to the rounding of that one step (--dump-outputs).
+    seeded = (eng.flat.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(), opt.step_count)
+
+    def restore_seeded_state():
+        eng.flat.copy_(seeded[0]); opt.exp_avg.copy_(seeded[1]); opt.exp_avg_sq.copy_(seeded[2])
+        opt.step_count = seeded[3]
+        eng.invalidate_weights()
+
     host_batch = None
     if args.inputs == "host":          # what the training loop's move_to(batch, device) costs per step
         host_batch = {k: {kk: vv.cpu().pin_memory() for kk, vv in v.items()} for k, v in batch.items()}
@@ -277,9 +343,12 @@ def main():
                 batch[k][kk].copy_(vv, non_blocking=True)
         return batch
 
+    last = {}          # the output dict of the latest step (--dump-outputs)
+
     def eager_step():
         cur = h2d() if host_batch is not None else batch
         out = model(cur)
+        last["out"] = out
         opt.zero_grad()
         out["loss"].backward()
         if dp is not None:
@@ -343,8 +412,9 @@ def main():
             opt.hyper_external = False
             eng.overlap_wgrad = eng.dbg["overlap_wgrad"]          # (GraphedStep switched the side stream off)
 
+    kernel_timing = args.full and not args.no_kernel_timing
     for w in range(args.warmup):
-        exclusive = w == 0 and not args.no_kernel_timing and args.warmup > 1 and not use_graph      # also warm the schedule the sampled steps use
+        exclusive = w == 0 and kernel_timing and args.warmup > 1 and not use_graph      # also warm the schedule the sampled steps use
         saved = eng.overlap_wgrad
         if exclusive:
             eng.overlap_wgrad = False
@@ -352,7 +422,6 @@ def main():
         eng.overlap_wgrad = saved
     timed = ("mca_attn_bwd_prep", "mca_attn_bwd_prep_onepass", "mca_attn_bwd_onepass", "mca_attn_vmean_if_needed", "mca_attn_vmean", "mca_layernorm_fwd", "mca_layernorm_bwd", "mca_attn_fwd", "mca_attn_fwd_fp8", "mca_attn_quant_mxfp8", "mca_attn_bwd_dq", "mca_attn_bwd_dkv", "mca_attn_bwd_dq_fp8", "mca_attn_bwd_dkv_fp8", "mca_attn_quant_bwd_mxfp8", "mca_gemm_nt", "mca_gemm_nt_lnres", "mca_gemm_nt_geglu_fwd", "mca_gemm_nt_geglu_bwd",
              "mca_gemm_tn_acc", "mca_gemm_tn_acc_group")
-    kernel_timing = not args.no_kernel_timing
     if graphed is not None and kernel_timing:
         # The sampled steps of a replayed loop run their body eagerly with an event pair around every launch.  That exact form is
         # run once here, outside the timed region: in a process that is not the first on its box the first such step stalls
@@ -367,13 +436,15 @@ def main():
     torch.cuda.synchronize()
     if kernel_timing:
         hip.profile_start(timed)
-    gpu_state = GpuStateSampler(dev.index if hasattr(dev, "index") and dev.index is not None else 0) if rank == 0 else None
+    gpu_state = GpuStateSampler(dev.index if hasattr(dev, "index") and dev.index is not None else 0) if rank == 0 and args.full else None
     if gpu_state is not None:
         gpu_state.start()
     t0 = time.perf_counter()
     sampled = 0
     host_marks = []          # --step-times: host clock after every step's launches (a sampled step ends synchronised)
     for i in range(args.steps):
+        if i == args.steps - 1:
+            restore_seeded_state()
         rec = kernel_timing and (i % args.sample_every) == 0
         hip.profile_enable(rec)
         sampled += int(rec)
@@ -383,8 +454,21 @@ def main():
             # event pair brackets ONE kernel's own duration; the other steps run the overlapped production schedule
             saved = eng.overlap_wgrad
             eng.overlap_wgrad = False
-        if graphed is not None:
-            loss = graphed.step(h2d() if host_batch is not None else None, eager=rec)          # (a sampled step of the replayed loop runs its body eagerly)
+        if graphed is not None and rec:
+            # a sampled step of the replayed loop runs its body eagerly; that body's output dict is kept for --dump-outputs
+            body = graphed._body
+
+            def kept_body():
+                last["out"] = body()
+                return last["out"]
+            graphed._body = kept_body
+            try:
+                loss = graphed.step(h2d() if host_batch is not None else None, eager=True)
+            finally:
+                del graphed._body          # (back to the class's method)
+        elif graphed is not None:
+            loss = graphed.step(h2d() if host_batch is not None else None)
+            last["out"] = graphed.out
         else:
             loss = step()
         if rec:
@@ -411,12 +495,14 @@ def main():
     # plausible and every gradient at 1e28: DESIGN.md section 5)
     gmax = float(eng.gflat.abs().max())
     assert gmax == gmax and gmax < 1e6, f"gradients of the last timed step are not sane (max |g| = {gmax})"
+    if args.dump_outputs and rank == 0:          # before anything else runs a step
+        dump_outputs(args.dump_outputs, model, last["out"])
 
     # Steady state, reported BESIDE the contract's figure (never as `value`): every process starts in the slower of the chip's two
     # sustained-load operating points and moves to the faster one after 12-27 s of unbroken load (profiles/r04_slow_regime.md), so
     # the K timed steps after W warm-up steps always measure the first; a training run lives in the second.
     sustained = None
-    if args.sustain_seconds > 0 and world == 1 and graphed is not None and host_batch is None:
+    if args.full and args.sustain_seconds > 0 and world == 1 and graphed is not None and host_batch is None:
         try:          # the contract's figure is already measured: nothing in this block may lose it
             window = args.sustain_seconds / 3.0
             t_s = time.perf_counter()
@@ -485,7 +571,7 @@ def main():
                                 "avg_launch_us": round(ms / n * 1e3, 1), "alg_flops_per_launch": fl / n,
                                 "sampled_steps": sampled}
             line["kernels"] = kern
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(P, args.workload, args.variant, args.cpu_protocol)
         print(json.dumps(line), flush=True)
     if world > 1:

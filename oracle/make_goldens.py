@@ -18,6 +18,7 @@ Fixtures
   ref_state/, ref_state_io.pt : a state directory in the layout of the reference's accelerator.save_state (model.safetensors,
                    optimizer.bin, scheduler.bin) after two reference training steps on a native-sized small model, the
                    embeddings / masks the reference's inference loop produces from it, and the reference's third step.
+                   Files above 1 MB are written as byte chunks <name>.part0, .part1, ... (split_fixture).
   cmu_<case>.pt  : CMU-shaped config (N=2538, D=512, L=5) at b=2 with weights from the build's own
                    deterministic initialiser; pooled embeddings, loss terms, per-parameter grad norms.
 """
@@ -369,6 +370,26 @@ def make_tcga(refmodel):
     print(f"tcga: loss {float(rec['loss']):.5f}, {len(rec['losses'])} terms, pooled {tuple(rec['pooled'].shape)}")
 
 
+PART_BYTES = 1_000_000          # no committed file is larger than 1 MiB: a larger fixture is committed as byte chunks
+
+
+def split_fixture(path):
+    """<path> -> <path>.part0, <path>.part1, ... (equal byte chunks of at most PART_BYTES) when it is larger than PART_BYTES;
+    tests/util_small.py golden_path() joins them again."""
+    import glob
+    for old in glob.glob(glob.escape(path) + ".part*"):
+        os.remove(old)
+    data = open(path, "rb").read()
+    if len(data) <= PART_BYTES:
+        return
+    n = -(-len(data) // PART_BYTES)
+    step = -(-len(data) // n)
+    for i in range(n):
+        with open(f"{path}.part{i}", "wb") as f:
+            f.write(data[i * step:(i + 1) * step])
+    os.remove(path)
+
+
 def make_ckpt(refmodel):
     """A state directory as the reference's ``accelerator.save_state`` lays it out (train_accel_gpu.py:122-123):
     model.safetensors (``safetensors.torch.save_file(model.state_dict())``, which is what Accelerate's save_model does),
@@ -427,6 +448,9 @@ def make_ckpt(refmodel):
     torch.save({"config": cfg, "train_batches": batches, "eval_batch": eval_batch, "embeddings": emb, "masks": masks,
                 "lr_step3": lr_next, "loss_step3": out["loss"].detach().clone(), "state_step3": after3},
                os.path.join(GOLD, "ref_state_io.pt"))
+    for f in ("model.safetensors", "optimizer.bin"):
+        split_fixture(os.path.join(out_dir, f))
+    split_fixture(os.path.join(GOLD, "ref_state_io.pt"))
     print("wrote ref_state/ and ref_state_io.pt:", {k: os.path.getsize(os.path.join(out_dir, k)) for k in os.listdir(out_dir)})
 
 

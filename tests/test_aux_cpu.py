@@ -3,6 +3,8 @@ import os
 
 import torch
 
+from util_small import golden_path
+
 
 def test_checkpoint_roundtrip_reference_layout(pkg, tmp_path):
     cfg = pkg.config.cmu_model_config(2)
@@ -127,20 +129,21 @@ def test_train_script_data_path_calls_setup_data():
         assert re.search(r"setup_data\(config\.dataset.*predrop=bool\(config\.get\(\"predrop\"", src, re.S), script
 
 
-def test_reference_written_state_dir_loads(pkg, golden_dir):
+def test_reference_written_state_dir_loads(pkg):
     """tests/golden/ref_state was written by the REFERENCE (oracle/make_goldens.py --ckpt: safetensors of its state_dict,
-    torch AdamW / cosine scheduler state): every key matches the native module tree, values load bit-exactly."""
+    torch AdamW / cosine scheduler state; its larger files are committed in byte chunks that golden_path joins): every key
+    matches the native module tree, values load bit-exactly."""
     from safetensors.torch import load_file
-    io = torch.load(os.path.join(golden_dir, "ref_state_io.pt"), weights_only=False)
+    io = torch.load(golden_path("ref_state_io.pt"), weights_only=False)
     m = pkg.MCA(**io["config"])
-    missing, unexpected = pkg.checkpoint.load_model(m, os.path.join(golden_dir, "ref_state"), strict=True)
+    missing, unexpected = pkg.checkpoint.load_model(m, golden_path("ref_state"), strict=True)
     assert not missing and not unexpected
-    sd = load_file(os.path.join(golden_dir, "ref_state", "model.safetensors"))
+    sd = load_file(os.path.join(golden_path("ref_state"), "model.safetensors"))
     own = m.state_dict()
     for k, v in sd.items():
         if k in own:
             assert torch.equal(own[k], v), k
-    opt = torch.load(os.path.join(golden_dir, "ref_state", "optimizer.bin"), weights_only=False)
+    opt = torch.load(os.path.join(golden_path("ref_state"), "optimizer.bin"), weights_only=False)
     assert len(opt["state"]) == len(list(m.parameters()))                # state index i = i-th model.parameters()
     for i, p in enumerate(m.parameters()):
         assert tuple(opt["state"][i]["exp_avg"].shape) == tuple(p.shape)

@@ -13,7 +13,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from conftest import GOLDEN, REPO
-from util_small import small_config, rel_err, to_device
+from util_small import small_config, rel_err, to_device, golden_path
 from conftest import REPO
 
 pytestmark = pytest.mark.gpu
@@ -35,11 +35,11 @@ def _pooled(model, out):
 
 # ------------------------------------------------------------------------------------------------ reference state dir
 def _load_ref_state(P):
-    io = torch.load(os.path.join(GOLDEN, "ref_state_io.pt"), weights_only=False)
+    io = torch.load(golden_path("ref_state_io.pt"), weights_only=False)
     optim = importlib.import_module("mca-paper_amd.optim")
     model = P.MCA(**copy.deepcopy(io["config"])).cuda()
     opt = optim.FusedAdamW(model, lr=1e-3)
-    meta = P.checkpoint.load_state(os.path.join(GOLDEN, "ref_state"), model, opt)
+    meta = P.checkpoint.load_state(golden_path("ref_state"), model, opt)
     return io, model, opt, meta
 
 

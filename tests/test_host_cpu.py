@@ -4,6 +4,7 @@ collators, and that the C-ABI library loads and exports every symbol include/mca
 import copy
 import ctypes
 import importlib
+import math
 import os
 import re
 import sys
@@ -92,7 +93,20 @@ def test_state_dict_keys_and_same_seed_init_as_reference(pkg):
     for k, (s, a, shape) in rec["checksums"].items():
         v = sd[k]
         assert tuple(v.shape) == tuple(shape), k
-        assert abs(float(v.double().sum()) - s) <= 1e-9 * max(1.0, abs(s)) and abs(float(v.double().abs().sum()) - a) <= 1e-9 * max(1.0, a), k
+        tol_s, tol_a = 1e-9 * max(1.0, abs(s)), 1e-9 * max(1.0, a)
+        if k.endswith("positional_encoder.pe"):
+            # The sinusoidal table takes no seed.  Its float32 exp / sin / cos come from the host's vector math library, whose
+            # code paths differ in the last bit (the goldens were recorded on one host; another CPU takes another path).  So: every
+            # element is the formula evaluated in fp64 within the float32 rounding of its frequency and angle (the angle error
+            # grows with the position) plus one ulp, and the sums agree with the reference's within one float32 ulp per element.
+            L, d = v.shape
+            freq = torch.exp(torch.arange(0, d, 2, dtype=torch.float64) * (-math.log(10000.0) / d))
+            ang = torch.arange(L, dtype=torch.float64).unsqueeze(1) * freq
+            want = torch.stack([torch.sin(ang), torch.cos(ang)], -1).reshape(L, d)
+            bound = torch.repeat_interleave(ang, 2, dim=1) * 2.0 ** -21 + 2.0 ** -22
+            assert bool(((v.double() - want).abs() <= bound).all()), k
+            tol_s = tol_a = float(v.double().abs().sum()) * 2.0 ** -23
+        assert abs(float(v.double().sum()) - s) <= tol_s and abs(float(v.double().abs().sum()) - a) <= tol_a, k
 
 
 def test_tiny_golden_state_loads_and_masks_match(pkg):

@@ -65,11 +65,28 @@ def test_tiny_case(case):
         else:
             _close(grads[n], g, 1e-4, 1e-7, f"grad {n}")
     _close(gn, rec["grad_norm"], 1e-5, 0, "grad norm")
-    # weights after step 1 and step 2 (AdamW + clip)
+    # weights after step 1 (AdamW + clip).  Adam's first step moves a weight by lr * u, u = c g / (c |g| + eps) (c: the clip
+    # factor): where c |g| ~ eps, u turns the fp32 noise of the gradient (checked above) into up to a whole step, and that noise
+    # depends on the host's math library (the goldens were recorded on one host).  So (a) every element where the first step is
+    # well conditioned (c |g| >= 100 eps) is compared directly, within a few % of one step; and (b) every element is compared
+    # with the difference that the two gradients explain, lr (u_mine - u_gold), taken out: what is left is the optimizer's own
+    # arithmetic, held to 1e-3 of one step.
+    lr = rec["lr"]
+
+    def u(g, norm):
+        cg = g.double() * min(1.0, rec["clip"] / (float(norm) + 1e-6))
+        return cg / (cg.abs() + 1e-8), cg.abs() >= 1e-6
+
     for n, v in rec["state_step1"].items():
-        # Adam's first step is lr*g/(|g|+eps): elements with |g| ~ eps amplify fp32 noise, so the
-        # absolute tolerance is a few % of one step (lr)
-        _close(sd[n], v, 1e-5, 5e-2 * rec["lr"], f"step1 {n}")
+        g = rec["grads"].get(n)
+        if g is None:
+            _close(sd[n], v, 0, 0, f"step1 {n} (no gradient: untouched)")
+            continue
+        u_mine, _ = u(grads[n], gn)
+        u_gold, cond = u(g, rec["grad_norm"])
+        if cond.any():
+            _close(sd[n][cond], v[cond], 1e-5, 5e-2 * lr, f"step1 {n} (well-conditioned elements)")
+        _close(sd[n].double() + lr * (u_mine - u_gold), v, 1e-5, 1e-3 * lr, f"step1 {n} (gradient difference taken out)")
     O.train_step(S, sd, rec["batch"], "fp32", lr=rec["lr"], clip=rec["clip"], opt_state=None)
 
 

@@ -13,7 +13,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from conftest import GOLDEN, REPO
-from util_small import small_config, rel_err, to_device
+from util_small import small_config, rel_err, to_device, golden_path
 from conftest import REPO
 
 pytestmark = pytest.mark.gpu
@@ -45,7 +45,7 @@ def test_infer_script_reproduces_reference_embeddings(P, tmp_path):
     {train,eval}_{embeddings,masks,labels}.pt in the reference's format (infer_accel_gpu.py:97-136)."""
     import yaml
     from datasets import Dataset
-    io = torch.load(os.path.join(GOLDEN, "ref_state_io.pt"), weights_only=False)
+    io = torch.load(golden_path("ref_state_io.pt"), weights_only=False)
     cfg, eb = io["config"], io["eval_batch"]
     samples = []
     for rep in range(2):
@@ -70,7 +70,7 @@ def test_infer_script_reproduces_reference_embeddings(P, tmp_path):
     y = dict(encoder_configs=cfg["encoder_configs"], modality_config=mod_cfg, hidden_size=cfg["dim"], layers=cfg["depth"], heads=cfg["heads"],
              dim_head=cfg["dim_head"], num_fusion_tokens=cfg["num_fusion_tokens"], batch_size=2, fcl=cfg["fcl"], fcl_root=cfg["fcl_root"],
              bimodal_contrastive=cfg["bimodal_contrastive"], non_fusion_fcl=cfg["non_fusion_fcl"], fusion_combos=cfg["fusion_combos"],
-             zorro=cfg["zorro"], dataset=ds_path, split=0.25, ds_seed=42, predrop=False, restart=os.path.join(GOLDEN, "ref_state"),
+             zorro=cfg["zorro"], dataset=ds_path, split=0.25, ds_seed=42, predrop=False, restart=golden_path("ref_state"),
              output_dir=str(tmp_path / "out"), label_col="Labels")
     ypath = tmp_path / "infer.yaml"
     ypath.write_text(yaml.safe_dump(y, sort_keys=False))          # the modality order IS the token order
@@ -342,13 +342,13 @@ def test_bench_ranks_report_their_launch_choice_and_collectives(world):
 
 
 def test_bench_single_gpu_line_follows_the_contract():
-    """`python bench.py --steps 4 --warmup 2` on one GPU (small batch, no CPU baseline: the contract's other fields): ONE JSON
+    """`python bench.py --full --steps 4 --warmup 2` on one GPU (small batch, no CPU baseline: the contract's other fields): ONE JSON
     line with BASELINE's metric and unit, whole-job value consistent with ms_per_step, `roofline` of the dominant launch class
     (achieved / peak = frac, live HIP events of the one eager sampled step), the workload named in `config`, the clock the figure was
     measured at, and the steady-state rate beside - never instead of - `value`."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--batch", "4", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--batch", "4", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
                         "--sustain-seconds", "3"], capture_output=True, text=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -367,3 +367,44 @@ def test_bench_single_gpu_line_follows_the_contract():
     su = rec["config"]["sustained"]
     assert su["samples_per_s"] > 0 and su["steps"] >= 50 and "not `value`" in su["note"]
     assert "cpu_baseline" not in rec and rec["kernels"]["mca_attn_bwd_dkv/layer"]["launches_per_step"] == 5
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """`python bench.py --steps 3 --warmup 1 --dump-outputs DIR` without --full: the contract's line and nothing measured beside it
+    (no roofline / per-kernel table, CPU baseline, clock sampling or sustained rate: every timed step is a replay), and the last
+    timed step's outputs as float32 .npy files within 64 MB: finite, shaped as the step's outputs, the weight and gradient
+    samples of equal size; a second run with the same arguments dumps the same outputs up to the rounding of one step."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    import numpy as np
+    dump = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--batch", "4", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=900, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["metric"].startswith("training samples/sec") and rec["unit"] == "samples/s" and rec["higher_is_better"] is True
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["dtype"] == "bf16" and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - 4 * 3 / (rec["ms_per_step"] * 3e-3)) <= 1e-2 * rec["value"]
+    assert not {"roofline", "kernels", "cpu_baseline"} & set(rec) and not {"sustained", "gpu_state_rank0"} & set(rec["config"])
+    assert rec["config"]["launch"] == "hipGraph replay (one launch per step)"
+    files = sorted(os.listdir(dump))
+    assert files == ["grads_sample.npy", "loss.npy", "loss_terms.npy", "pooled.npy", "weights_sample.npy"], files
+    arrays = {f[:-4]: np.load(dump / f) for f in files}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["loss"].shape == () and arrays["loss_terms"].ndim == 1 and arrays["pooled"].shape[0] == 4 and arrays["pooled"].shape[2] == 512
+    assert arrays["weights_sample"].shape == arrays["grads_sample"].shape and np.abs(arrays["grads_sample"]).max() > 0
+    # same arguments, another process: the dumped step starts from the same seeded state, so the forward's outputs agree bit for
+    # bit and the gradients / updated weights up to the rounding of that one step (the order of the weight-gradient atomics)
+    dump2 = tmp_path / "out2"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--batch", "4", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(dump2)], capture_output=True, text=True, timeout=900, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-2000:]
+    again = {f[:-4]: np.load(dump2 / f) for f in files}
+    for k in ("loss", "loss_terms", "pooled"):
+        assert np.array_equal(arrays[k], again[k]), k
+    for k in ("grads_sample", "weights_sample"):
+        a, b = arrays[k].astype(np.float64), again[k].astype(np.float64)
+        assert np.linalg.norm(a - b) <= 1e-5 * np.linalg.norm(b), (k, float(np.linalg.norm(a - b) / np.linalg.norm(b)))

@@ -1,8 +1,53 @@
 """Helpers shared by the GPU parity tests, smoke() and bench: a small configuration the native kernels
 accept (dim = heads*64) and runners for the native step and the oracle step."""
+import atexit
 import copy
+import os
+import re
+import shutil
+import tempfile
 
 import torch
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+_PART = re.compile(r"\.part\d+$")
+_joined = {}
+
+
+def golden_path(name):
+    """Path of the fixture tests/golden/<name>, a file or a directory of files.  A fixture file above the repository's limit of
+    1 MiB per file is committed as byte chunks <file>.part0, <file>.part1, ... (oracle/make_goldens.py split_fixture); such a
+    fixture is joined once per process into a temporary directory, and the path of that byte-identical copy is returned."""
+    src = os.path.join(GOLDEN, name)
+    if name in _joined:
+        return _joined[name]
+    if os.path.isfile(src) or (os.path.isdir(src) and not any(_PART.search(f) for f in os.listdir(src))):
+        return src
+    tmp = tempfile.mkdtemp(prefix="mca_golden_")
+    atexit.register(shutil.rmtree, tmp, True)
+    dst = os.path.join(tmp, name)
+    if os.path.isdir(src):
+        os.makedirs(dst)
+        for f in sorted(os.listdir(src)):
+            if f.endswith(".part0"):
+                _join(os.path.join(src, f[:-len(".part0")]), os.path.join(dst, f[:-len(".part0")]))
+            elif not _PART.search(f):
+                shutil.copy(os.path.join(src, f), dst)
+    else:
+        _join(src, dst)
+    _joined[name] = dst
+    return dst
+
+
+def _join(stem, dst):
+    i = 0
+    with open(dst, "wb") as out:
+        while os.path.exists(f"{stem}.part{i}"):
+            with open(f"{stem}.part{i}", "rb") as f:
+                out.write(f.read())
+            i += 1
+    if i == 0:
+        raise FileNotFoundError(f"{stem} (nor {stem}.part0)")
 
 
 def small_config(variant="mca", depth=2):
