@@ -396,6 +396,48 @@ int mca_adamw_step(float* p, const float* g, float* m, float* v, int64_t n,
  * mca_adamw_hyper, a one-thread kernel launched outside the graph (scalar arguments: no host buffer to race with).      */
 int mca_adamw_hyper(float* hyper, float lr, float bias_corr1, float bias_corr2, mca_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Downstream evaluation (lp_accel_gpu.py of the reference: utils/metrics.py:20-27,72-98 and its probe loop), fp32, no float
+ * atomics: the same bits on every launch.  The tile-core products (cosine rank, pair sum, the probe's NT layer and TN
+ * gradients) are one k-ordered fmaf chain per output; the row kernels (normalisation, probe head) add lane-strided partials
+ * in a fixed xor tree (csrc/evaluate.hip).
+ * --------------------------------------------------------------------------------------------- */
+/* y[i] = x[i] / max(||x[i]||_2, 1e-8) for n rows of d (torch's cosine_similarity order: normalise, then dot).  y may be x. */
+int mca_rows_normalize_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t n, int64_t d, mca_stream_t stream);
+/* rank[r] = #{ j < nt : q[i].t[j] > q[i].t[i] } with i = qidx[r] (or r when qidx is NULL), for r < nq: the rank of the true
+ * target among all targets, strict > (exact ties do not count).  s_true: nq floats of workspace, = q[i].t[i] by the same
+ * fmaf chain as the tile.  Every qidx[r] must be a row of q and < nt (the caller checks).  Integer atomics only.           */
+int mca_cosine_rank_f32(const float* q, int64_t ldq, const int32_t* qidx, int64_t nq, const float* t, int64_t ldt, int64_t nt,
+                        int64_t d, float* s_true, int32_t* rank, mca_stream_t stream);
+/* doubles of workspace mca_pair_gauss_sum_f32 needs for n rows */
+int64_t mca_pair_gauss_workspace(int64_t n);
+/* sum_out[0] = sum_{i<j} exp(-t * ||x_i - x_j||^2) (exp in fp32, the squared distance a direct-difference fmaf chain, fp64
+ * per-tile partials added in a fixed order); value_out[0] = log(sum / (n (n - 1) / 2)) as float: lunif of the reference
+ * (NaN for n < 2, -inf when every pair underflows).  Either output may be NULL.                                       */
+int mca_pair_gauss_sum_f32(const float* x, int64_t ldx, int64_t n, int64_t d, float t, double* partials, int64_t n_partials,
+                           double* sum_out, float* value_out, mca_stream_t stream);
+/* Probe layer: y[m, n] = act(x[xidx[m]] . w[n] + bias[n]) (xidx may be NULL, bias may be NULL); act 0 none, 1 ReLU, 2 dropout
+ * (keep when a hash of (seed, step, m, n) >= p, kept values scaled by 1/(1-p)) then ReLU.                                   */
+int mca_probe_nt_f32(const float* x, int64_t ldx, const int32_t* xidx, const float* w, int64_t ldw, const float* bias, float* y,
+                     int64_t ldy, int64_t M, int64_t N, int64_t K, int act, float p, uint64_t seed, int64_t step, mca_stream_t stream);
+/* number of loss partials mca_probe_head_f32 writes for B rows */
+int64_t mca_probe_head_blocks(int64_t B);
+/* Probe head over B rows: z[r] = a[aidx[r]] . w[l] + bias[l] (w [L, K]), pred[r, l] = z; loss_type 0 L1, 1 MSE, 2 BCE with
+ * logits against labels[yidx[r], l] (labels [*, L]); dz (may be NULL) = d(mean loss)/dz; da (may be NULL) [B, K] =
+ * (dz . w)[r, k] * dact_scale where a[r, k] > 0, else 0 (ReLU + dropout backward of the MLP's stored hidden output);
+ * loss_part[mca_probe_head_blocks(B)] = per-block sums of the element losses.  K <= 1024, L <= 64.                     */
+int mca_probe_head_f32(const float* a, int64_t lda, const int32_t* aidx, int64_t K, const float* w, const float* bias, int64_t L,
+                       const float* labels, const int32_t* yidx, int64_t B, int loss_type, float* pred, float* dz, float* da,
+                       float dact_scale, float* loss_part, mca_stream_t stream);
+/* floats of workspace mca_probe_tn_f32 needs */
+int64_t mca_probe_tn_workspace(int64_t R, int64_t N, int64_t K);
+/* gw[m, k] = sum_r a[r, m] * b[bidx[r], k] and gb[m] = sum_r a[r, m] over R rows (a weight and bias gradient; bidx may be
+ * NULL): per-chunk partials of 128 rows, added in chunk order by a second launch.                                       */
+int mca_probe_tn_f32(const float* a, int64_t lda, const float* b, int64_t ldb, const int32_t* bidx, int64_t R, int64_t N, int64_t K,
+                     float* partials, int64_t n_partials, float* gw, float* gb, mca_stream_t stream);
+/* acc[0] += (sum of n loss partials, fixed order) / count */
+int mca_probe_loss_accum(const float* loss_part, int64_t n, int64_t count, float* acc, mca_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@ Reference: utils/config.py:9-61 (defaults), :76-93 (YAML overlay; unknown keys a
 """
 from __future__ import annotations
 
+import ast
 import copy
 import os
 from datetime import datetime
@@ -60,6 +61,75 @@ def training_config(filename: str, make_output_dir: bool = True) -> Config:
         os.makedirs(cfg["output_dir"], exist_ok=True)
         with open(os.path.join(cfg["output_dir"], "config.yaml"), "w") as f:
             yaml.safe_dump(dict(cfg), f)
+    return cfg
+
+
+def get_cfg_defaults_embedding_eval() -> Config:
+    """The probe's defaults: utils/config.py:129-153 of the reference, same 19 keys and values."""
+    return Config(
+        embedding_dir="", task=0, loss_type="L1", model_type="linear", hidden_size=256, dropout=0.1, wandb_name="MCA",
+        lr=1e-5, lr_scheduler_type="cosine", num_warmup_steps=1000, rank_metrics=True, epochs=1024, clip=2.0, metric="PCC",
+        output_dir="", wandb_job_name="MCA-DefaultJobName", seed=42, batch_size=1024, threshold=0.0,
+    )
+
+
+def _decode_value(v):
+    """yacs' _decode_cfg_value: strings go through literal decoding (``"1e-4"`` -> 1e-4), anything that is no literal stays
+    a string; nested dicts are decoded key by key."""
+    if isinstance(v, dict):
+        return Config({k: _decode_value(x) for k, x in v.items()})
+    if not isinstance(v, str):
+        return v
+    try:
+        return ast.literal_eval(v)
+    except (ValueError, SyntaxError):
+        return v
+
+
+def _merge_yacs(dst: Config, src: Dict[str, Any]) -> None:
+    """yacs CfgNode.merge_from_other_cfg with new keys allowed: a value whose type differs from the default's raises
+    ValueError unless yacs converts it (tuple <-> list); keys the defaults lack are kept."""
+    for k, raw in src.items():
+        v = _decode_value(raw)
+        if k in dst:
+            old = dst[k]
+            if isinstance(old, dict) and isinstance(v, dict):
+                _merge_yacs(old, v)
+                continue
+            if type(v) is not type(old):
+                if isinstance(v, tuple) and isinstance(old, list):
+                    v = list(v)
+                elif isinstance(v, list) and isinstance(old, tuple):
+                    v = tuple(v)
+                else:
+                    raise ValueError(f"Type mismatch ({type(old)} vs. {type(v)}) with values ({old} vs. {v}) for config key: {k}")
+        dst[k] = v
+
+
+def _plain(v):
+    if isinstance(v, dict):
+        return {k: _plain(x) for k, x in v.items()}
+    if isinstance(v, tuple):
+        return [_plain(x) for x in v]
+    return v
+
+
+def embedding_eval_config(filename: str) -> Config:
+    """utils/config.py:155-170: the defaults, a timestamped output directory chosen BEFORE the YAML is merged (so an
+    ``output_dir`` in the YAML wins), the merge with yacs' rules, then ``config.yaml`` dumped into the output directory."""
+    cfg = get_cfg_defaults_embedding_eval()
+    with open(filename, "r") as f:
+        overlay = yaml.safe_load(f) or {}
+    if not cfg.output_dir:
+        base = datetime.now().strftime("training_output_%H_%M_%d_%m_%Y")
+        cfg.output_dir, i = base, 1
+        while os.path.isdir(cfg.output_dir):
+            cfg.output_dir = f"{base}_{i}"
+            i += 1
+    _merge_yacs(cfg, overlay)
+    os.makedirs(cfg.output_dir, exist_ok=True)
+    with open(os.path.join(cfg.output_dir, "config.yaml"), "w") as f:
+        yaml.safe_dump(_plain(dict(cfg)), f)
     return cfg
 
 

@@ -165,6 +165,16 @@ SIGNATURES = {
     "mca_adamw_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P]),
     "mca_adamw_hyper": (_I, [_P, _F, _F, _F, _P]),
     "mca_nonfinite_flag": (_I, [C.POINTER(FiniteArgs), _P, _I, _P]),
+    "mca_rows_normalize_f32": (_I, [_P, _I64, _P, _I64, _I64, _I64, _P]),
+    "mca_cosine_rank_f32": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "mca_pair_gauss_workspace": (_I64, [_I64]),
+    "mca_pair_gauss_sum_f32": (_I, [_P, _I64, _I64, _I64, _F, _P, _I64, _P, _P, _P]),
+    "mca_probe_nt_f32": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I, _F, C.c_uint64, _I64, _P]),
+    "mca_probe_head_blocks": (_I64, [_I64]),
+    "mca_probe_head_f32": (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I, _P, _P, _P, _F, _P, _P]),
+    "mca_probe_tn_workspace": (_I64, [_I64, _I64, _I64]),
+    "mca_probe_tn_f32": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, _I64, _P, _P, _P]),
+    "mca_probe_loss_accum": (_I, [_P, _I64, _I64, _P, _P]),
 }
 # measurement hooks (include/mca_hip_debug.h): exported by the library, not part of the drop-in ABI
 DEBUG_SIGNATURES = {

@@ -1,9 +1,14 @@
 """Embedding-space metrics of the reference's eval loop (utils/metrics.py:20-70, Wang & Isola 2020): alignment of
 positive pairs and uniformity on the hypersphere, accumulated over batches like the reference's torchmetrics classes
-(``update`` / ``compute(norm=...)`` / ``reset``).  Plain torch; evaluation only, not on the timed step."""
+(``update`` / ``compute(norm=...)`` / ``reset``).  Plain torch; evaluation only, not on the timed step.
+
+The probe stage (lp_accel_gpu.py) adds: the retrieval rank metrics of the reference (utils/metrics.py:72-98:
+``compute_cosines``, ``get_rank``, ``get_rank_metrics``) on the HIP rank kernel, ``uniformity`` (``lunif`` on the HIP pair
+kernel), ``__call__`` on the two accumulators (torchmetrics' forward), and the per-epoch formulas of the probe's torchmetrics
+(binary classification scores, Pearson correlation) as device tensor code without host syncs."""
 from __future__ import annotations
 
-from typing import List
+from typing import Dict, List
 
 import torch
 from torch.nn.functional import normalize
@@ -51,6 +56,11 @@ class Alignment:
             return lalign(_gather_cat(self.preds, group), _gather_cat(self.target, group), self.alpha, norm)
         return lalign(torch.cat(self.preds), torch.cat(self.target), self.alpha, norm)
 
+    def __call__(self, preds: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """torchmetrics' forward: the rows are accumulated, and the value of THIS call's rows is returned (norm=False)."""
+        self.update(preds, target)
+        return lalign(preds.float(), target.float(), self.alpha, False)
+
     def reset(self):
         self.preds, self.target = [], []
 
@@ -68,5 +78,186 @@ class Uniformity:
             return lunif(_gather_cat(self.preds, group), self.t, norm)
         return lunif(torch.cat(self.preds), self.t, norm)
 
+    def __call__(self, preds: torch.Tensor) -> torch.Tensor:
+        """torchmetrics' forward: the rows are accumulated, and the value of THIS call's rows is returned (norm=False), on the
+        HIP pair kernel (``uniformity``)."""
+        self.update(preds)
+        return uniformity(preds, self.t, False)
+
     def reset(self):
         self.preds = []
+
+
+# ---- HIP-backed retrieval and uniformity (csrc/evaluate.hip) --------------------------------------------------------------
+def _hip():
+    import importlib
+    return importlib.import_module("mca-paper_amd.hip")
+
+
+def _hip_device(device=None) -> torch.device:
+    """The HIP device the kernels below run on: the current one (``device``, when given, must name it).  The library reads
+    device memory only, so a request it cannot serve raises ValueError here, before anything is launched."""
+    if device is not None:
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError(f"the evaluation kernels run on a HIP device, not on {dev}")
+    if not torch.cuda.is_available():
+        raise ValueError("the evaluation kernels need a HIP device and none is available (the inputs stay on the cpu)")
+    cur = torch.device("cuda", torch.cuda.current_device())
+    if device is not None and dev.index is not None and dev.index != cur.index:
+        raise ValueError(f"device {dev} is not the current HIP device {cur}: the kernels launch on its current stream")
+    return cur
+
+
+def _device_f32(x: torch.Tensor, device: torch.device) -> torch.Tensor:
+    """x as a contiguous fp32 (rows, features) tensor on ``device`` (a ``_hip_device``): cpu inputs are copied there."""
+    if x.dim() != 2:
+        raise ValueError(f"expected a 2-D (rows, features) tensor, got {tuple(x.shape)}")
+    return x.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def normalize_rows(x: torch.Tensor) -> torch.Tensor:
+    """x / max(||x||_2, 1e-8) per row, fp32 on the current HIP device (cpu inputs are copied there): the first half of
+    torch's cosine_similarity."""
+    h = _hip()
+    x = _device_f32(x, _hip_device())
+    y = torch.empty_like(x)
+    h.call("mca_rows_normalize_f32", x.data_ptr(), x.shape[1], y.data_ptr(), x.shape[1], x.shape[0], x.shape[1], h.stream_ptr())
+    return y
+
+
+def uniformity(x: torch.Tensor, t: float = 2, norm: bool = True) -> torch.Tensor:
+    """``lunif`` of the same rows on the HIP pair kernel: log of the mean over pairs i < j of exp(-t ||x_i - x_j||^2), the
+    squared distance taken as a direct-difference fmaf chain (no pdist sqrt then square), exp in fp32, the sum in fp64.
+    A 0-d fp32 tensor on the current HIP device (cpu inputs are copied there): NaN for fewer than two rows, -inf when every
+    pair underflows (as the pdist form)."""
+    h = _hip()
+    x = _device_f32(x, _hip_device())
+    if norm:
+        x = normalize_rows(x)
+    n, d = x.shape
+    ws = torch.empty(h.lib().mca_pair_gauss_workspace(n), dtype=torch.float64, device=x.device)
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    h.call("mca_pair_gauss_sum_f32", x.data_ptr(), d, n, max(d, 1), float(t), ws.data_ptr(), ws.numel(), None, out.data_ptr(),
+           h.stream_ptr())
+    return out
+
+
+def cosine_ranks(queries: torch.Tensor, targets: torch.Tensor, index: torch.Tensor, device=None) -> torch.Tensor:
+    """ranks[r] = #{j : cos(q_i, t_j) > cos(q_i, t_i)}, i = index[r]: the rank of the true target (row i of targets) among
+    all targets, strict > as the reference's get_rank.  int32 on the HIP device (``_hip_device(device)``; cpu inputs are
+    copied there); cosines as torch's cosine_similarity takes them (rows normalised, then one fmaf chain per dot product;
+    the true target's value is bitwise the matrix's)."""
+    h = _hip()
+    dev = _hip_device(device)
+    q, t = normalize_rows(_device_f32(queries, dev)), normalize_rows(_device_f32(targets, dev))
+    if q.shape[1] != t.shape[1]:
+        raise ValueError(f"queries have {q.shape[1]} features, targets {t.shape[1]}")
+    idx = index.detach().to(device="cpu", dtype=torch.int64)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= min(q.shape[0], t.shape[0])):
+        raise IndexError("every selected query needs its true target: row i of queries pairs with row i of targets")
+    idx = idx.to(device=dev, dtype=torch.int32)
+    s_true = torch.empty(idx.numel(), dtype=torch.float32, device=dev)
+    ranks = torch.empty(idx.numel(), dtype=torch.int32, device=dev)
+    h.call("mca_cosine_rank_f32", q.data_ptr(), q.shape[1], idx.data_ptr(), idx.numel(), t.data_ptr(), t.shape[1], t.shape[0], t.shape[1],
+           s_true.data_ptr(), ranks.data_ptr(), h.stream_ptr())
+    return ranks
+
+
+def compute_cosines(embedding: torch.Tensor, embeddings: torch.Tensor) -> torch.Tensor:
+    """utils/metrics.py:73-76: cosine of one vector against every row, (rows,) fp32 on the current HIP device, without the
+    reference's (rows, D) repeat: normalised rows times the normalised vector on the HIP probe layer kernel."""
+    h = _hip()
+    dev = _hip_device()
+    t = normalize_rows(_device_f32(embeddings, dev))
+    q = normalize_rows(_device_f32(embedding.reshape(1, -1), dev))
+    out = torch.empty(t.shape[0], 1, dtype=torch.float32, device=dev)
+    h.call("mca_probe_nt_f32", t.data_ptr(), t.shape[1], None, q.data_ptr(), q.shape[1], None, out.data_ptr(), 1, t.shape[0], 1, t.shape[1],
+           0, 0.0, 0, 0, h.stream_ptr())
+    return out.reshape(-1)
+
+
+def get_rank(x: torch.Tensor, indices) -> torch.Tensor:
+    """utils/metrics.py:78-80: per row of a (queries, targets) similarity matrix, how many entries exceed the true one."""
+    idx = torch.as_tensor(indices, device=x.device, dtype=torch.long)
+    vals = x[torch.arange(len(x), device=x.device), idx]
+    return (x > vals[:, None]).long().sum(1)
+
+
+def get_rank_metrics(embeddings: torch.Tensor, mask: torch.Tensor, targets: torch.Tensor, fusion: str = "fusion", device="cuda"):
+    """utils/metrics.py:82-98: (median rank, R@1, R@5, R@10) over the queries the mask selects, query i's positive being row
+    i of ``targets``.  0-d tensors on the HIP device: the median is torch.median's (the lower middle value), the recalls
+    fractions.  No selected query raises RuntimeError; a ``device`` that is not the current HIP device raises ValueError
+    (cpu inputs are copied to it)."""
+    _hip_device(device)                                 # a device the kernels cannot run on raises before any work
+    sel = torch.nonzero(torch.as_tensor(mask).reshape(-1).to("cpu").bool()).reshape(-1)
+    if sel.numel() == 0:
+        raise RuntimeError("get_rank_metrics: the mask selects no query")
+    ranks = cosine_ranks(embeddings, targets, sel, device).long()
+    n = float(ranks.numel())
+    return ranks.median(), (ranks == 0).sum() / n, (ranks < 5).sum() / n, (ranks < 10).sum() / n
+
+
+# ---- the probe's torchmetrics, per epoch on device tensors ------------------------------------------------------------------
+BINARY_METRICS = ("precision", "recall", "accuracy", "cm", "f1", "specificity", "auroc", "auprc")
+
+
+def binary_format(preds: torch.Tensor, batch_rows: int, row_width: int) -> torch.Tensor:
+    """torchmetrics' binary input rule, per update: a batch (``batch_rows`` rows of ``row_width`` predictions, the last batch
+    possibly shorter) any of whose predictions lies outside [0, 1] is taken as logits and goes through a sigmoid."""
+    p = preds.reshape(-1).float()
+    per = batch_rows * row_width
+    bid = torch.arange(p.numel(), device=p.device) // per
+    nb = (p.numel() + per - 1) // per
+    bad = torch.zeros(nb, device=p.device).scatter_reduce(0, bid, ((p < 0) | (p > 1)).float(), reduce="amax", include_self=True)
+    return torch.where(bad[bid] > 0, torch.sigmoid(p), p)
+
+
+def _safe_div(a, b):
+    return torch.where(b > 0, a / b.clamp_min(1), torch.zeros_like(a))
+
+
+def binary_metrics(probs: torch.Tensor, target: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The eight binary torchmetrics of the probe (lp_accel_gpu.py:105-115) from formatted predictions (``binary_format``)
+    and 0/1 targets, flattened: threshold 0.5 (pred = p > 0.5), zero division -> 0, cm = [[TN, FP], [FN, TP]].  auroc and
+    auprc are exact (no binning; sklearn's roc_auc_score / average_precision_score, ties as one threshold).  An epoch of a
+    single class returns auroc 0 and, with no positive, auprc 0 (with only positives auprc is 1)."""
+    p = probs.reshape(-1).double()
+    y = target.reshape(-1).long()
+    hard = (p > 0.5).long()
+    tp = ((hard == 1) & (y == 1)).sum().double()
+    fp = ((hard == 1) & (y == 0)).sum().double()
+    fn = ((hard == 0) & (y == 1)).sum().double()
+    tn = ((hard == 0) & (y == 0)).sum().double()
+    out = {"precision": _safe_div(tp, tp + fp), "recall": _safe_div(tp, tp + fn),
+           "accuracy": _safe_div(tp + tn, tp + tn + fp + fn), "f1": _safe_div(2 * tp, 2 * tp + fp + fn),
+           "specificity": _safe_div(tn, tn + fp),
+           "cm": torch.stack([torch.stack([tn, fp]), torch.stack([fn, tp])]).long()}
+    # exact curves: scores in descending order, one point per distinct score (the last index of each run of ties)
+    order = torch.argsort(p, descending=True, stable=True)
+    ps, ys = p[order], y[order].double()
+    n = ps.numel()
+    pos = torch.arange(1, n + 1, device=p.device, dtype=torch.float64)
+    tps = torch.cumsum(ys, 0)
+    fps = pos - tps
+    last = torch.ones(n, dtype=torch.bool, device=p.device)
+    last[:-1] = ps[1:] != ps[:-1]
+    first = torch.ones(n, dtype=torch.bool, device=p.device)
+    first[1:] = ps[1:] != ps[:-1]
+    start = torch.cummax(torch.where(first, torch.arange(n, device=p.device), torch.zeros(n, dtype=torch.long, device=p.device)), 0).values
+    prev = start - 1                                            # the previous distinct score's last index (-1: the origin)
+    tp_prev = torch.where(prev >= 0, tps[prev.clamp_min(0)], torch.zeros_like(tps))
+    fp_prev = torch.where(prev >= 0, fps[prev.clamp_min(0)], torch.zeros_like(fps))
+    P, N = tps[-1], fps[-1]
+    lastf = last.double()
+    area = ((fps - fp_prev) * (tps + tp_prev) * 0.5 * lastf).sum()
+    out["auroc"] = _safe_div(area, P * N)
+    out["auprc"] = _safe_div(((tps - tp_prev) * (tps / pos) * lastf).sum(), P)
+    return {k: (v if k == "cm" else v.float()) for k, v in out.items()}
+
+
+def pearson(preds: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """Pearson correlation of the flattened predictions and targets over the epoch (fp64 moments, an fp32 0-d result)."""
+    x, y = preds.reshape(-1).double(), target.reshape(-1).double()
+    xc, yc = x - x.mean(), y - y.mean()
+    return ((xc * yc).sum() / ((xc * xc).sum().sqrt() * (yc * yc).sum().sqrt())).float()
