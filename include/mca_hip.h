@@ -316,11 +316,13 @@ int mca_attn_bwd_dkv_fp8(const mca_attn_bwd2_args* args, const mca_attn_fp8_bwd_
  * operands (khot / qblk: at most 15 key groups), MCA_ATTN_Q_PRESCALED, nq == nk == n.  Tables (structure.build_onepass_schedule):
  *   qt_desc[n_qtiles]  = {first row, rows (1..64)}                       query tiles, a partition of 0..n-1
  *   kb_desc[n_kblocks] = {first key, keys (1..256), first entry, entries} key blocks, a partition of 0..n-1, 16-byte aligned
- *   kb_qt[]            = per key block its query tiles | (every pair structurally allowed << 31), ascending
+ *   kb_qt[]            = per key block its query tiles | (every pair structurally allowed << 31); the order inside a block's
+ *                        list is free (a tile's first / last visit is decided per key block): the generator emits serpentine
  *   visit[n_kblocks][n_qtiles] = 1 where the block lists the tile;  max_list = longest list (<= 250), n_entries = all lists
  * rowc (b, heads, n_qtiles + 1, 2, 64) fp32: -lse | -delta of the tile's rows (mca_attn_bwd_prep_onepass; positions past a
- * tile's rows, and the whole last tile - the NULL tile every key block's sweep ends on - hold -inf | 0, written once by the caller).  dq_acc: workspace of batch * heads * (n_qtiles + 1) * 4096 floats (the last slot of a
- * (sample, head) belongs to the null tile: written, never read back into a result), contents irrelevant on entry.  dq, dk, dv bf16, every element written.  n_qtiles < 256, n_kblocks <= 64, max_list <= 250, else MCA_E_UNSUPPORTED
+ * tile's rows, and the whole last tile - the NULL tile every key block's sweep ends on - hold -inf | 0, written once by the caller).  dq_acc: workspace of
+ * batch * heads * max(1, split) * (n_qtiles + 1) * 4096 floats (the last slot of a (sample, head) belongs to the null tile:
+ * written, never read back into a result), contents irrelevant on entry.  dq, dk, dv bf16, every element written.  n_qtiles < 256, n_kblocks <= 64, max_list <= 250, else MCA_E_UNSUPPORTED
  * (the caller keeps the two-pass form).                                                                                  */
 typedef struct {
   const uint16_t* q; int64_t q_bstride; int64_t q_ld;           /* q[b*q_bstride + head*q_hstride + i*q_ld + d]                       */
@@ -340,8 +342,8 @@ typedef struct {
   float scale;
   int flags;
   int split;                                                   /* 0 / 1: one workgroup per (sample, head).  S = 2..8 (small batches): S workgroups per  */
-                                                               /* (sample, head), key block kb swept by workgroup kb mod S, dq_acc holds S slices of   */
-                                                               /* batch * heads * (n_qtiles + 1) slots (slice-major per (sample, head)), summed in      */
+                                                               /* (sample, head), key block kb swept by workgroup kb mod S, dq_acc holds S slices  */
+                                                               /* per (sample, head) (slice-major; total size: see dq_acc above), summed in            */
                                                                /* slice order by a second launch of the same call: still no atomics, bitwise repeatable  */
 } mca_attn_bwd1_args;
 int mca_attn_bwd_onepass(const mca_attn_bwd1_args* args, mca_stream_t stream);

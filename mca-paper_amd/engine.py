@@ -25,7 +25,8 @@ from typing import Callable, Dict, List, Optional
 import numpy as np
 import torch
 
-from . import hip
+from . import attention, hip
+from .attention import AttnGrads, AttnOperands, _OnePassSched, _Sched, _dev
 from .encoders import EmbeddedSequenceEncoder, TabularEncoder
 from .hip import AttnBwd1Args, AttnBwd2Args, AttnFp8BwdOperands, AttnFp8Operands, AttnFwdArgs, LossTerm, call, ptr, stream_ptr
 
@@ -36,10 +37,6 @@ BWD_BQ = 64          # query rows per step of the dK/dV pass (its key-block size
 
 def _pad_to(x: int, m: int) -> int:
     return (x + m - 1) // m * m
-
-
-def _dev(a: np.ndarray, device) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
 
 
 def debug_options() -> dict:
@@ -58,36 +55,6 @@ def debug_options() -> dict:
             raise ValueError(f"MCA_DEBUG: unknown switch '{k}' (known: {sorted(opts)})")
         opts[k] = int(v) if k == "dkv_keys" else (v.strip() not in ("0", "", "false"))
     return opts
-
-
-class _Sched:
-    """device copies of a TileSchedule"""
-
-    def __init__(self, s, device):
-        self.s = s
-        # tile index with the "structurally full" flag in bit 31: one scalar load per tile in the kernels
-        pack = lambda idx, full: (idx.astype(np.uint32) | (full.astype(np.uint32) << 31)).view(np.int32)
-        self.q_ptr, self.q_kt, self.q_order = _dev(s.q_ptr, device), _dev(pack(s.q_kt, s.q_full), device), _dev(s.q_order, device)
-        self.k_ptr, self.k_qt, self.k_order = _dev(s.k_ptr, device), _dev(pack(s.k_qt, s.k_full), device), _dev(s.k_order, device)
-        # per launch slot of the backward: {key block, first entry, number of entries, query tile of the first entry}
-        wg = np.zeros((len(s.k_order), 4), np.int32)
-        for i, kb in enumerate(s.k_order):
-            lo, hi = int(s.k_ptr[kb]), int(s.k_ptr[kb + 1])
-            wg[i] = (kb, lo, hi - lo, int(s.k_qt[lo]) if hi > lo else 0)
-        self.k_wg = _dev(wg, device)
-
-
-class _OnePassSched:
-    """device copies of a structure.OnePassSchedule (mca_attn_bwd_onepass)"""
-
-    def __init__(self, s, device):
-        self.s = s
-        self.qt_desc, self.kb_desc = _dev(s.qt_desc.astype(np.int32), device), _dev(s.kb_desc.astype(np.int32), device)
-        self.kb_qt = _dev(s.kb_qt.astype(np.uint32).view(np.int32), device)
-        self.visit, self.row_slot = _dev(s.visit.astype(np.uint8), device), _dev(s.row_slot.astype(np.int32), device)
-        self.n_qt, self.n_kb, self.max_list = len(s.qt_desc), len(s.kb_desc), int(s.kb_desc[:, 3].max())
-        self.n_entries = int(len(s.kb_qt))
-        self.fits = self.n_qt < 256 and self.n_kb <= 64 and self.max_list + 6 <= 256 and self.n_entries + 4 * self.n_kb <= 768          # the kernel's LDS tables
 
 
 class FusionEngine:
@@ -314,8 +281,22 @@ class FusionEngine:
         fresh = ws.get(("fp8gen", layer)) == ws["gen"]
         return ws[key][1], (0b1100 if fresh else 0b1111)
 
+    def backward_plan(self, ws, b, nq, dq_f32=False) -> attention.Plan:
+        """attention.backward_plan for an attention with nq query rows at batch b: the ONLY place the engine decides the backward
+        form.  The mask product is a property of the workspace (ws = None: of the workspace this engine would build); the
+        MCA_DEBUG switch is read now, not at construction."""
+        sc = self.sched_onepass
+        return attention.backward_plan(
+            attn_dtype=self.attn_dtype, mask_product=self.mask_mfma if ws is None else ws.get("khot") is not None,
+            onepass_tables_fit=sc is not None, onepass_want=self.dbg["onepass"], dkv_keys=self.dkv_keys, b=b, heads=self.H,
+            n_kblocks=sc.n_kb if sc is not None else 1, layer_attention=nq == self.N, dq_f32=dq_f32)
+
+    def backward_form(self, b) -> str:
+        """what the layer attention's backward runs at batch b (reported by bench.py)"""
+        return attention.describe(self.backward_plan(None, b, self.N))
+
     def fp8_backward_on(self, ws, nq) -> bool:
-        return self.attn_dtype == "fp8" and nq == self.N and ws.get("khot") is not None and self.dkv_keys == 128
+        return self.backward_plan(ws, ws["b"], nq).form == "fp8-twopass"
 
     def invalidate_weights(self):
         """Call after writing parameters through an alias autograd's version counters cannot see (``p.data.op_()``, a raw
@@ -411,6 +392,16 @@ class FusionEngine:
         ws["dg"], ws["do"] = bf(T, Ip), bf(T, D)
         ws["dpool_b"], ws["dop"], ws["dqp32"], ws["dqp_sum"], ws["dqp_b"] = bf(b * R, D), bf(b * R, D), f32(b * R, D), f32(R, D), bf(R, D)
         ws["dkvp"], ws["drt"] = (None if self.eao else bf(T, 2 * D)), f32(R, D)
+        sc = self.sched_onepass
+        if sc is not None:          # the one-pass attention backward's buffers, dq_acc sized by the split of this batch
+            rc = f32(b, H, sc.n_qt + 1, 2, 64)          # (+ the null tile)
+            rc[:, :, :, 0] = float("-inf"); rc[:, :, :, 1] = 0.0          # positions past a tile's rows: -inf | 0 (written once; the prep kernel only touches real rows)
+            ws["rowc"] = rc
+            ws["dq_acc"] = f32(b * H * self.backward_plan(ws, b, N).split * (sc.n_qt + 1) * 4096)          # (+ the null tile's slot)
+            # head-major packed copies of q and dO (written by the prep launch): a query tile of a head is contiguous memory
+            # (+ 64 rows: the kernel reads whole 64-row tiles, the last one past its rows)
+            ws["q_hm"] = torch.zeros((b * H * N + 64) * 64, dtype=torch.bfloat16, device=dev)
+            ws["do_hm"] = torch.zeros((b * H * N + 64) * 64, dtype=torch.bfloat16, device=dev)
         ws["enc"] = {}
         for mi, name in enumerate(self.model.modality_types):
             enc = self.model.encoders[name]
@@ -471,70 +462,84 @@ class FusionEngine:
              ptr(rowmask), ptr(dx), dx.stride(0) if dx is not None else 0, ptr(dx_bf16),
              dx_bf16.stride(0) if dx_bf16 is not None else 0, ptr(dgamma), ptr(dbeta), ptr(dxsum), rows, cols, stream_ptr())
 
-    def _attn_fwd(self, q, q_bstride, q_ld, kv, k_off, v_off, kv_ld, o, lse, qmask, sched, ws, b, nq, layer=0):
-        N = self.N
-        a = AttnFwdArgs()
-        esz = 2
-        a.q, a.q_bstride, a.q_ld = q, q_bstride, q_ld
-        a.k, a.v = kv.data_ptr() + k_off * esz, kv.data_ptr() + v_off * esz
-        a.kv_bstride, a.kv_ld = N * kv_ld, kv_ld
-        a.o, a.o_bstride, a.o_ld = o.data_ptr(), nq * o.stride(0), o.stride(0)
-        a.lse = lse.data_ptr()
-        a.qmask, a.keyinfo, a.ktile_flags = qmask.data_ptr(), ws["keyinfo"].data_ptr(), ws["kflags"].data_ptr()
+    def layer_attention(self, ws, i):
+        """-> (AttnOperands, AttnGrads) of fusion layer i: q | k | v and dq | dk | dv are the column blocks of the packed (T, 3D)
+        qkv / dqkv matrices"""
+        D, N, a = self.D, self.N, ws["layers"][i]
+        return (AttnOperands(a["qkv"].data_ptr(), N * 3 * D, 3 * D, a["qkv"], D, 2 * D, 3 * D, a["o"], a["lse"], N, self.qmask_attn,
+                             self.qblk_attn, self.sched_attn_f, self.sched_attn_b2, i),
+                AttnGrads(ws["do"], ws["delta"], a["dqkv"].data_ptr(), N * 3 * D, 3 * D, False, a["dqkv"], D, 2 * D, 3 * D))
+
+    def pool_attention(self, ws):
+        """-> (AttnOperands, AttnGrads) of the attentive pooling: one (R, D) q for every sample, k | v packed as (T, 2D), dq fp32"""
+        D, R = self.D, self.R
+        return (AttnOperands(ws["qp"].data_ptr(), 0, D, ws["kvp"], 0, D, 2 * D, ws["op"], ws["lse_p"], R, self.qmask_pool,
+                             self.qblk_pool, self.sched_pool_f, self.sched_pool_b2, None),
+                AttnGrads(ws["dop"], ws["delta_p"], ws["dqp32"].data_ptr(), R * D, D, True, ws["dkvp"], 0, D, 2 * D))
+
+    def _attn_common(self, a, ops, ws, q=None):
+        """the fields AttnFwdArgs, AttnBwd2Args and AttnBwd1Args share (q: another (pointer, batch stride, leading dimension))"""
+        a.q, a.q_bstride, a.q_ld = q or (ops.q, ops.q_bstride, ops.q_ld)
+        kv = ops.kv.data_ptr()
+        a.k, a.v, a.kv_bstride, a.kv_ld = kv + ops.k_off * 2, kv + ops.v_off * 2, self.N * ops.kv_ld, ops.kv_ld
+        a.keyinfo, a.ktile_flags = ws["keyinfo"].data_ptr(), ws["kflags"].data_ptr()
+        if ws.get("khot") is not None:
+            a.khot = ws["khot"].data_ptr()
+            if hasattr(a, "qblk"):
+                a.qblk = ops.qblk.data_ptr()
+        a.batch, a.heads, a.nk_pad, a.scale, a.flags = ws["b"], self.H, self.nk_pad, self.scale, self.attn_flags
+        return a
+
+    def attn_forward(self, ops, ws):
+        N, b, sched = self.N, ws["b"], ops.sched_f
+        a = self._attn_common(AttnFwdArgs(), ops, ws)
+        a.o, a.o_bstride, a.o_ld = ops.o.data_ptr(), ops.nq * ops.o.stride(0), ops.o.stride(0)
+        a.lse, a.qmask, a.vmean = ops.lse.data_ptr(), ops.qmask.data_ptr(), ws["vmean"].data_ptr()
         a.q_ptr, a.q_kt, a.q_order = sched.q_ptr.data_ptr(), sched.q_kt.data_ptr(), sched.q_order.data_ptr()
-        a.vmean = ws["vmean"].data_ptr()
-        a.batch, a.heads, a.nq, a.nk, a.nk_pad = b, self.H, nq, N, self.nk_pad
-        a.n_qtiles, a.n_ktiles, a.scale, a.flags = sched.s.n_q, sched.s.n_k, self.scale, self.attn_flags
-        a.khot = ws["khot"].data_ptr() if ws.get("khot") is not None else None
+        a.nq, a.nk, a.n_qtiles, a.n_ktiles = ops.nq, N, sched.s.n_q, sched.s.n_k
         # mean(V) is the output of fully masked rows only: samples with every modality present have none and are skipped
         if ws.get("present_cur") is not None:
             call("mca_attn_vmean_if_needed", a.v, a.kv_bstride, a.kv_ld, ws["vmean"].data_ptr(), b, N, self.H, ptr(ws["present_cur"]),
                  (1 << self.M) - 1, stream_ptr())
         else:
             call("mca_attn_vmean", a.v, a.kv_bstride, a.kv_ld, ws["vmean"].data_ptr(), b, N, self.H, stream_ptr())
-        hip.set_tag("pool" if nq != N else "layer")
-        if self.attn_dtype == "fp8" and nq == N:
-            f = self._fp8_operands(ws, b, layer)[1]
-            ws[("fp8gen", layer)] = ws["gen"]
+        hip.set_tag("pool" if ops.nq != N else "layer")
+        if self.attn_dtype == "fp8" and ops.nq == N:
+            f = self._fp8_operands(ws, b, ops.layer)[1]
+            ws[("fp8gen", ops.layer)] = ws["gen"]
             call("mca_attn_quant_mxfp8", a.q, a.q_bstride, a.q_ld, a.k, a.v, a.kv_bstride, a.kv_ld, C.byref(f), b, self.H, N, stream_ptr())
             call("mca_attn_fwd_fp8", C.byref(a), C.byref(f), stream_ptr(), flops=4.0 * 64 * sched.s.allowed_pairs * self.H * b)
         else:
             call("mca_attn_fwd", C.byref(a), stream_ptr(), flops=4.0 * 64 * sched.s.allowed_pairs * self.H * b)
         hip.set_tag("")
 
-    def _attn_bwd2(self, q, q_bstride, q_ld, kv, k_off, v_off, kv_ld, o, d_o, lse, delta, dq_ptr, dq_bstride, dq_ld, dq_f32, dkv,
-                   dk_off, dv_off, dkv_ld, qmask, sched_f, sched_b, ws, b, nq, layer=0):
-        """two-pass backward (attention_bwd2.hip): dq (bf16 or fp32) is WRITTEN, not accumulated.  The layer attention at a
-        batch that gives every CU a (sample, head) takes the one-pass form (attention_bwd1.hip) instead."""
-        N, esz = self.N, 2
-        if self.use_onepass(ws, b, nq, dq_f32):
-            return self._attn_bwd1(q, q_bstride, q_ld, kv, k_off, v_off, kv_ld, o, d_o, lse, dq_ptr, dq_bstride, dq_ld, dkv, dk_off, dv_off,
-                                   dkv_ld, ws, b)
-        call("mca_attn_bwd_prep", o.data_ptr(), d_o.data_ptr(), nq * o.stride(0), o.stride(0), lse.data_ptr(),
-             delta.data_ptr(), ws["dvmean"].data_ptr(), b, self.H, nq, N, stream_ptr())
-        a = AttnBwd2Args()
-        a.q, a.q_bstride, a.q_ld = q, q_bstride, q_ld
-        a.k, a.v = kv.data_ptr() + k_off * esz, kv.data_ptr() + v_off * esz
-        a.kv_bstride, a.kv_ld = N * kv_ld, kv_ld
+    def attn_backward(self, ops, grads, ws):
+        """The attention backward in the form backward_plan names.  Two-pass (attention_bwd2.hip): dq (bf16 or fp32) is WRITTEN,
+        not accumulated.  The layer attention at a batch that gives every CU a (sample, head) takes the one-pass form."""
+        N, b, nq, sched_f, sched_b = self.N, ws["b"], ops.nq, ops.sched_f, ops.sched_b
+        plan = self.backward_plan(ws, b, nq, grads.dq_f32)
+        if plan.form == "onepass":
+            return self._attn_backward_onepass(ops, grads, ws, plan.split)
+        o, d_o = ops.o, grads.d_o
+        call("mca_attn_bwd_prep", o.data_ptr(), d_o.data_ptr(), nq * o.stride(0), o.stride(0), ops.lse.data_ptr(),
+             grads.delta.data_ptr(), ws["dvmean"].data_ptr(), b, self.H, nq, N, stream_ptr())
+        a = self._attn_common(AttnBwd2Args(), ops, ws)
         a.d_o, a.o_bstride, a.o_ld = d_o.data_ptr(), nq * d_o.stride(0), d_o.stride(0)
-        a.lse, a.delta, a.dvmean = lse.data_ptr(), delta.data_ptr(), ws["dvmean"].data_ptr()
-        a.dq, a.dq_bstride, a.dq_ld, a.dq_f32 = dq_ptr, dq_bstride, dq_ld, int(dq_f32)
-        a.dk, a.dv = dkv.data_ptr() + dk_off * esz, dkv.data_ptr() + dv_off * esz
-        a.dkv_bstride, a.dkv_ld = N * dkv_ld, dkv_ld
-        a.qmask, a.keyinfo, a.ktile_flags = qmask.data_ptr(), ws["keyinfo"].data_ptr(), ws["kflags"].data_ptr()
+        a.lse, a.delta, a.dvmean = ops.lse.data_ptr(), grads.delta.data_ptr(), ws["dvmean"].data_ptr()
+        a.dq, a.dq_bstride, a.dq_ld, a.dq_f32 = grads.dq, grads.dq_bstride, grads.dq_ld, int(grads.dq_f32)
+        dkv = grads.dkv.data_ptr()
+        a.dk, a.dv, a.dkv_bstride, a.dkv_ld = dkv + grads.dk_off * 2, dkv + grads.dv_off * 2, N * grads.dkv_ld, grads.dkv_ld
+        a.qmask = ops.qmask.data_ptr()
         a.q_ptr, a.q_kt, a.q_order = sched_f.q_ptr.data_ptr(), sched_f.q_kt.data_ptr(), sched_f.q_order.data_ptr()
         a.n_qtiles128, a.n_ktiles64 = sched_f.s.n_q, sched_f.s.n_k
         a.k_wg, a.k_qt, a.n_qtiles64, a.n_kblocks256 = sched_b.k_wg.data_ptr(), sched_b.k_qt.data_ptr(), sched_b.s.n_q, sched_b.s.n_k
-        a.batch, a.heads, a.nq, a.nk, a.nk_pad, a.scale, a.flags = b, self.H, nq, N, self.nk_pad, self.scale, self.attn_flags
-        if ws.get("khot") is not None:
-            a.khot, a.qblk = ws["khot"].data_ptr(), (self.qblk_attn if qmask is self.qmask_attn else self.qblk_pool).data_ptr()
-        a.kblock_keys = sched_b.s.bk
+        a.nq, a.nk, a.kblock_keys = nq, N, sched_b.s.bk
         pairs = sched_b.s.allowed_pairs
         hip.set_tag("pool" if nq != N else "layer")
         # algorithmic flops of the whole backward (2 x forward) split 3 : 5 over the passes by their share of the five
         # products a one-pass backward needs (dq pass: S, dP, dQ minus the recomputed S, dP counted once)
-        if self.fp8_backward_on(ws, nq):
-            f, which = self._fp8_bwd_operands(ws, b, layer)
+        if plan.form == "fp8-twopass":
+            f, which = self._fp8_bwd_operands(ws, b, ops.layer)
             call("mca_attn_quant_bwd_mxfp8", a.q, a.q_bstride, a.q_ld, a.k, a.v, a.kv_bstride, a.kv_ld, a.d_o, a.o_bstride, a.o_ld,
                  C.byref(f), which, b, self.H, N, stream_ptr())
             call("mca_attn_bwd_dkv_fp8", C.byref(a), C.byref(f), stream_ptr(), flops=8.0 * 64 * pairs * self.H * b * 0.6)
@@ -544,62 +549,25 @@ class FusionEngine:
             call("mca_attn_bwd_dq", C.byref(a), stream_ptr(), flops=8.0 * 64 * pairs * self.H * b * 0.4)
         hip.set_tag("")
 
-    ONEPASS_MIN_WG = 192          # (sample, head) pairs from which the one-pass backward is the default: one workgroup per CU
-
-    def use_onepass(self, ws, b, nq, dq_f32=False) -> bool:
-        """The one-pass bf16 backward wherever it applies - also with fp8 attention operands: it is faster than the two-pass backward
-        with fp8 score recomputes (LONG b = 128: 9.1 against 10.5 ms per layer), so `set_attention_dtype("fp8")` then means the fp8
-        forward + this backward; the fp8 two-pass backward remains for small batches (and MCA_DEBUG=onepass=0)."""
-        if self.sched_onepass is None or nq != self.N or dq_f32 or ws.get("khot") is None:
-            return False
-        want = self.dbg["onepass"]
-        return bool(want) if want is not None else b * self.H * self.onepass_split(b) >= self.ONEPASS_MIN_WG
-
-    def onepass_split(self, b) -> int:
-        """workgroups per (sample, head) of the one-pass backward: 1 where the batch gives every CU a (sample, head), else up to 4
-        (key blocks dealt round robin, partial dQ sums added by the call's second launch) - b = 8, 8 heads: 4 x 64 = 256 workgroups"""
-        wg = b * self.H
-        return 1 if wg >= self.ONEPASS_MIN_WG else max(1, min(4, self.sched_onepass.n_kb if self.sched_onepass else 1, -(-256 // wg)))
-
-    def backward_form(self, b) -> str:
-        """what the layer attention's backward runs at batch b (reported by bench.py)"""
-        ws = {"khot": True if self.mask_mfma else None}
-        if self.use_onepass(ws, b, self.N):
-            return "bf16 one-pass" + (f" (key blocks split {self.onepass_split(b)} ways)" if self.onepass_split(b) > 1 else "")
-        return "fp8 two-pass" if (self.attn_dtype == "fp8" and self.mask_mfma and self.dkv_keys == 128) else "bf16 two-pass"
-
-    def _attn_bwd1(self, q, q_bstride, q_ld, kv, k_off, v_off, kv_ld, o, d_o, lse, dq_ptr, dq_bstride, dq_ld, dkv, dk_off, dv_off, dkv_ld, ws, b):
+    def _attn_backward_onepass(self, ops, grads, ws, split):
         """one-pass backward of the layer attention (attention_bwd1.hip): dq, dk, dv bf16, every element written"""
-        N, esz, sc = self.N, 2, self.sched_onepass
-        if "rowc" not in ws:          # positions past a tile's rows: -inf | 0 (written once; the prep kernel only touches real rows)
-            rc = torch.empty(b, self.H, sc.n_qt + 1, 2, 64, dtype=torch.float32, device=self.device)          # (+ the null tile)
-            rc[:, :, :, 0] = float("-inf"); rc[:, :, :, 1] = 0.0
-            ws["rowc"] = rc
-            ws["dq_acc"] = torch.empty(b * self.H * self.onepass_split(b) * (sc.n_qt + 1) * 4096, dtype=torch.float32, device=self.device)          # (+ the null tile's slot)
-            # head-major packed copies of q and dO (written by the prep launch): a query tile of a head is contiguous memory
-            # (+ 64 rows: the kernel reads whole 64-row tiles, the last one past its rows)
-            ws["q_hm"] = torch.zeros((b * self.H * N + 64) * 64, dtype=torch.bfloat16, device=self.device)
-            ws["do_hm"] = torch.zeros((b * self.H * N + 64) * 64, dtype=torch.bfloat16, device=self.device)
-        call("mca_attn_bwd_prep_onepass", o.data_ptr(), d_o.data_ptr(), N * o.stride(0), o.stride(0), lse.data_ptr(), sc.row_slot.data_ptr(),
-             ws["rowc"].data_ptr(), ws["dvmean"].data_ptr(), b, self.H, N, sc.n_qt, q, q_bstride, q_ld, ws["q_hm"].data_ptr(),
-             ws["do_hm"].data_ptr(), stream_ptr())
-        a = AttnBwd1Args()
-        a.q, a.q_bstride, a.q_hstride, a.q_ld = ws["q_hm"].data_ptr(), self.H * N * 64, N * 64, 64
-        a.k, a.v = kv.data_ptr() + k_off * esz, kv.data_ptr() + v_off * esz
-        a.kv_bstride, a.kv_ld = N * kv_ld, kv_ld
-        a.d_o, a.o_bstride, a.o_hstride, a.o_ld = ws["do_hm"].data_ptr(), self.H * N * 64, N * 64, 64
-        a.rowc, a.dvmean = ws["rowc"].data_ptr(), ws["dvmean"].data_ptr()
-        a.dq, a.dq_bstride, a.dq_ld = dq_ptr, dq_bstride, dq_ld
-        a.dk, a.dv = dkv.data_ptr() + dk_off * esz, dkv.data_ptr() + dv_off * esz
-        a.dkv_bstride, a.dkv_ld = N * dkv_ld, dkv_ld
-        a.dq_acc = ws["dq_acc"].data_ptr()
-        a.keyinfo, a.ktile_flags, a.khot, a.qblk = ws["keyinfo"].data_ptr(), ws["kflags"].data_ptr(), ws["khot"].data_ptr(), self.qblk_attn.data_ptr()
+        N, H, b, sc, o = self.N, self.H, ws["b"], self.sched_onepass, ops.o
+        assert ws["dq_acc"].numel() >= b * H * split * (sc.n_qt + 1) * 4096, "dq_acc of this workspace is too small for the split"
+        call("mca_attn_bwd_prep_onepass", o.data_ptr(), grads.d_o.data_ptr(), N * o.stride(0), o.stride(0), ops.lse.data_ptr(),
+             sc.row_slot.data_ptr(), ws["rowc"].data_ptr(), ws["dvmean"].data_ptr(), b, H, N, sc.n_qt, ops.q, ops.q_bstride, ops.q_ld,
+             ws["q_hm"].data_ptr(), ws["do_hm"].data_ptr(), stream_ptr())
+        a = self._attn_common(AttnBwd1Args(), ops, ws, q=(ws["q_hm"].data_ptr(), H * N * 64, 64))
+        a.q_hstride = N * 64
+        a.d_o, a.o_bstride, a.o_hstride, a.o_ld = ws["do_hm"].data_ptr(), H * N * 64, N * 64, 64
+        a.rowc, a.dvmean, a.dq_acc = ws["rowc"].data_ptr(), ws["dvmean"].data_ptr(), ws["dq_acc"].data_ptr()
+        a.dq, a.dq_bstride, a.dq_ld = grads.dq, grads.dq_bstride, grads.dq_ld
+        dkv = grads.dkv.data_ptr()
+        a.dk, a.dv, a.dkv_bstride, a.dkv_ld = dkv + grads.dk_off * 2, dkv + grads.dv_off * 2, N * grads.dkv_ld, grads.dkv_ld
         a.qt_desc, a.kb_desc, a.kb_qt, a.visit = sc.qt_desc.data_ptr(), sc.kb_desc.data_ptr(), sc.kb_qt.data_ptr(), sc.visit.data_ptr()
         a.n_qtiles, a.n_kblocks, a.max_list, a.n_entries = sc.n_qt, sc.n_kb, sc.max_list, sc.n_entries
-        a.batch, a.heads, a.n, a.nk_pad, a.n_ktiles64 = b, self.H, N, self.nk_pad, (N + 63) // 64
-        a.scale, a.flags, a.split = self.scale, self.attn_flags, self.onepass_split(b)
+        a.n, a.n_ktiles64, a.split = N, (N + 63) // 64, split
         hip.set_tag("layer")
-        call("mca_attn_bwd_onepass", C.byref(a), stream_ptr(), flops=8.0 * 64 * sc.s.allowed_pairs * self.H * b)
+        call("mca_attn_bwd_onepass", C.byref(a), stream_ptr(), flops=8.0 * 64 * sc.s.allowed_pairs * H * b)
         hip.set_tag("")
 
     # ------------------------------------------------------------------------------------------------
@@ -735,8 +703,7 @@ class FusionEngine:
             g = ly.norm.gamma
             self.ln_fwd(xin, g, T, D, a["m1"], a["r1"], y=None if ln_in_gemm else ws["xn"], ldy=D, y_bf16=a["xn_b"], cols_pad=D)
             self.gemm_nt(a["xn_b"], w["qkv"], a["qkv"], T, 3 * D, D)
-            self._attn_fwd(a["qkv"].data_ptr(), N * 3 * D, 3 * D, a["qkv"], D, 2 * D, 3 * D, a["o"], a["lse"],
-                           self.qmask_attn, self.sched_attn_f, ws, b, N, layer=i)
+            self.attn_forward(self.layer_attention(ws, i)[0], ws)
             if ln_in_gemm:
                 call("mca_gemm_nt_lnres", ptr(a["o"]), D, ptr(w["o"]), D, ptr(a["x1"]), D, ptr(xin), D, ptr(a["m1"]), ptr(a["r1"]),
                      ptr(g.data), T, D, D, stream_ptr(), flops=2.0 * T * D * D)
@@ -762,8 +729,7 @@ class FusionEngine:
         self.gemm_nt(ws["t_b"], self.wp["kv"], ws["kvp"], T, 2 * D, D)
         call("mca_f32_to_bf16", ptr(m.return_tokens.data), D, ptr(ws["rt_b"]), D, R, D, 1.0, stream_ptr())
         self.gemm_nt(ws["rt_b"], self.wp["q"], ws["qp"], R, D, D)
-        self._attn_fwd(ws["qp"].data_ptr(), 0, D, ws["kvp"], 0, D, 2 * D, ws["op"], ws["lse_p"], self.qmask_pool,
-                       self.sched_pool_f, ws, b, R)
+        self.attn_forward(self.pool_attention(ws)[0], ws)
         self.gemm_nt(ws["op"], self.wp["o"], ws["pooled"], b * R, D, D, residual=m.return_tokens.data, res_period=R)
         return ws["pooled"]
 
@@ -849,9 +815,7 @@ class FusionEngine:
         self.gemm_nt(ws["dpool_b"], self.wp["oT"], ws["dop"], b * R, D, D)
         on_side(lambda: tn(ws["dpool_b"], ws["op"], G(ap.to_out.weight), b * R, D, D))
         # pooling attention
-        self._attn_bwd2(ws["qp"].data_ptr(), 0, D, ws["kvp"], 0, D, 2 * D, ws["op"], ws["dop"], ws["lse_p"], ws["delta_p"],
-                        ws["dqp32"].data_ptr(), R * D, D, True, ws["dkvp"], 0, D, 2 * D, self.qmask_pool, self.sched_pool_f,
-                        self.sched_pool_b2, ws, b, R)
+        self.attn_backward(*self.pool_attention(ws), ws)
         ws["dqp_sum"].zero_()
         call("mca_reduce_rows", ptr(ws["dqp32"]), D, R * D, R, ptr(ws["dqp_sum"]), D, b * R, D, stream_ptr())
         call("mca_f32_to_bf16", ptr(ws["dqp_sum"]), D, ptr(ws["dqp_b"]), D, R, D, 1.0, stream_ptr())
@@ -915,9 +879,7 @@ class FusionEngine:
                 on_side(lambda dx1=dx1, a=a, ly=ly: tn(dx1, a["o"], G(ly.attn.to_out.weight), T, D, D))
             self.gemm_nt(dx1, w["oT"], ws["do"], T, D, D)
             # dq | dk | dv land in dqkv as bf16, each element written once
-            self._attn_bwd2(a["qkv"].data_ptr(), N * 3 * D, 3 * D, a["qkv"], D, 2 * D, 3 * D, a["o"], ws["do"], a["lse"],
-                            ws["delta"], dqkv.data_ptr(), N * 3 * D, 3 * D, False, dqkv, D, 2 * D, 3 * D, self.qmask_attn,
-                            self.sched_attn_f, self.sched_attn_b2, ws, b, N, layer=i)
+            self.attn_backward(*self.layer_attention(ws, i), ws)
             # to_q.weight and to_kv.weight are adjacent in the flat gradient buffer: one (3D, D) weight-gradient GEMM
             gq = G(ly.attn.to_q.weight)
             assert G(ly.attn.to_kv.weight).data_ptr() == gq.data_ptr() + D * D * 4

@@ -277,3 +277,60 @@ def test_onepass_schedule_is_the_generated_one_and_hazard_free(tmp_path):
     probs2, n_owned = audit.audit_owned(text)
     assert n_owned > 100 and not probs2, probs2[:5]
     assert not audit.audit_m0(text)
+
+
+def test_attention_backward_plan_on_the_real_structures(pkg):
+    """attention.backward_plan, the one place the attention backward's form is decided, against values worked out by hand from its
+    rules (one-pass from 192 workgroups = (sample, head) pairs x split; split 1 from 192 pairs, else min(4, key blocks,
+    ceil(256 / pairs))) and the tables of the real structures (CMU / MMA 11 key blocks, TCGA 13, LONG 25: all fit the kernel's LDS;
+    EAO 159 query tiles, 42 key blocks, 940 entries: they do not)."""
+    A = importlib.import_module("mca-paper_amd.attention")
+    from util_small import small_config
+    C_ = pkg.config
+
+    def tables(cfg):
+        st = pkg.build_model(dict(cfg, depth=1)).structure
+        return st, A._OnePassSched(st.attn_onepass_schedule(aligned=True), "cpu")
+
+    def plan(sc, b, heads=8, **kw):
+        args = dict(attn_dtype="bf16", mask_product=True, onepass_tables_fit=sc.fits, onepass_want=None, dkv_keys=128, b=b, heads=heads,
+                    n_kblocks=sc.n_kb, layer_attention=True, dq_f32=False)
+        args.update(kw)
+        return A.backward_plan(**args)
+
+    two_pass_below = {1, 2, 3, 4}
+    split_of = {6: 4, 8: 4, 16: 2, 24: 1, 32: 1, 128: 1}
+    for cfg, n_kb in ((C_.cmu_model_config(), 11), (C_.cmu_model_config(zorro=True), 11), (C_.tcga_model_config(), 13),
+                      (C_.cmu_model_config(long_seq=True), 25)):
+        st, sc = tables(cfg)
+        assert sc.fits and sc.n_kb == n_kb and int(st.kgroup.max()) <= 14          # (the mask product is on)
+        for b in two_pass_below:
+            assert plan(sc, b).form == "bf16-twopass" and plan(sc, b, attn_dtype="fp8").form == "fp8-twopass"
+        for b, split in split_of.items():
+            assert plan(sc, b) == A.Plan("onepass", split)
+            assert plan(sc, b, attn_dtype="fp8") == A.Plan("onepass", split)          # fp8 forward + bf16 one-pass backward
+            for b_ in (b, 2):
+                assert plan(sc, b_, attn_dtype="fp8", onepass_want=False).form == "fp8-twopass"
+                assert plan(sc, b_, onepass_want=False).form == "bf16-twopass"
+                assert plan(sc, b_, attn_dtype="fp8", onepass_want=False, dkv_keys=256).form == "bf16-twopass"
+                assert plan(sc, b_, attn_dtype="fp8", mask_product=False).form == "bf16-twopass"
+                # the pooling attention: never one-pass, never fp8
+                for kw in (dict(layer_attention=False, dq_f32=True), dict(layer_attention=False), dict(dq_f32=True)):
+                    for dt in ("bf16", "fp8"):
+                        for want in (None, True, False):
+                            assert plan(sc, b_, attn_dtype=dt, onepass_want=want, **kw).form == "bf16-twopass"
+        assert plan(sc, 2, onepass_want=True) == A.Plan("onepass", 4)          # MCA_DEBUG=onepass=1 forces the form, not the split
+    # the small test config: 2 heads, one key block
+    st, sc = tables(small_config("mca"))
+    assert (st.n_tokens, sc.n_kb, sc.fits) == (153, 1, True)
+    assert plan(sc, 6, heads=2) == A.Plan("bf16-twopass", 1) and plan(sc, 6, heads=2, attn_dtype="fp8") == A.Plan("fp8-twopass", 1)
+    # EAO: the tables do not fit the kernel's LDS
+    st, sc = tables(C_.cmu_eao_model_config())
+    assert (st.n_tokens, sc.n_qt, sc.n_kb, sc.n_entries, sc.fits) == (9800, 159, 42, 940, False)
+    for b in (1, 8, 32, 128):
+        assert plan(sc, b).form == "bf16-twopass" and plan(sc, b, onepass_want=True).form == "bf16-twopass"
+        assert plan(sc, b, attn_dtype="fp8").form == "fp8-twopass"
+    # what bench.py prints as config.attention_backward
+    assert A.describe(A.Plan("onepass", 1)) == "bf16 one-pass"
+    assert A.describe(A.Plan("onepass", 4)) == "bf16 one-pass (key blocks split 4 ways)"
+    assert A.describe(A.Plan("fp8-twopass", 4)) == "fp8 two-pass" and A.describe(A.Plan("bf16-twopass", 1)) == "bf16 two-pass"

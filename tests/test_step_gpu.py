@@ -384,11 +384,13 @@ def test_forward_bitwise_deterministic_at_cmu_size(P, b, lengths, p_drop):
                 assert torch.equal(x, y), f"tensor {i} differs between two forwards of the same inputs"
 
 
-@pytest.mark.parametrize("variant", ["mca", "mma"])
-def test_attention_backward_bitwise_deterministic_at_cmu_size(P, variant):
-    """The two-pass attention backward has one owner per output element: with the whole chip busy (b = 32) two launches on
-    the same operands agree BIT FOR BIT (dq, dk, dv).  A mis-counted wait in the hand-pipelined fragment reads would show
-    here as a few differing elements that every tolerance lets through."""
+@pytest.mark.parametrize("variant,onepass,form", [("mca", None, "onepass"), ("mma", None, "onepass"), ("mca", False, "bf16-twopass"),
+                                                  ("mma", False, "bf16-twopass")], ids=["mca", "mma", "mca-twopass", "mma-twopass"])
+def test_attention_backward_bitwise_deterministic_at_cmu_size(P, variant, onepass, form):
+    """Both bf16 forms of the layer attention's backward - the one-pass kernel this batch takes by default and the two-pass kernels
+    (MCA_DEBUG onepass=0) - have one owner per output element: with the whole chip busy (b = 32) two launches on the same operands
+    agree BIT FOR BIT (dq, dk, dv).  A mis-counted wait in the hand-pipelined fragment reads would show here as a few differing
+    elements that every tolerance lets through."""
     b = 32
     cfg = P.config.cmu_model_config(batch_size=b, zorro=variant == "mma")
     cfg["depth"] = 1
@@ -402,13 +404,13 @@ def test_attention_backward_bitwise_deterministic_at_cmu_size(P, variant):
     out["loss"].backward()
     ws = eng.workspace(b)
     a = ws["layers"][0]
-    N, D = eng.N, eng.D
+    eng.dbg["onepass"] = onepass
+    assert eng.backward_plan(ws, b, eng.N).form == form
+    ops, grads = eng.layer_attention(ws, 0)
     snaps = []
     for rep in range(3):
         a["dqkv"].fill_(7.0)
-        eng._attn_bwd2(a["qkv"].data_ptr(), N * 3 * D, 3 * D, a["qkv"], D, 2 * D, 3 * D, a["o"], ws["do"], a["lse"], ws["delta"],
-                       a["dqkv"].data_ptr(), N * 3 * D, 3 * D, False, a["dqkv"], D, 2 * D, 3 * D, eng.qmask_attn, eng.sched_attn_f,
-                       eng.sched_attn_b2, ws, b, N)
+        eng.attn_backward(ops, grads, ws)
         torch.cuda.synchronize()
         snaps.append(a["dqkv"].clone())
     assert torch.isfinite(snaps[0].float()).all()
@@ -417,6 +419,49 @@ def test_attention_backward_bitwise_deterministic_at_cmu_size(P, variant):
     assert bool(torch.isinf(a["lse"]).any())          # uniform rows exist: the dvmean path is exercised
     for s_ in snaps[1:]:
         assert torch.equal(s_, snaps[0])
+
+
+ATTN_ENTRY_POINTS = ("mca_attn_fwd", "mca_attn_fwd_fp8", "mca_attn_quant_mxfp8", "mca_attn_bwd_prep", "mca_attn_bwd_prep_onepass",
+                     "mca_attn_bwd_onepass", "mca_attn_bwd_dq", "mca_attn_bwd_dkv", "mca_attn_quant_bwd_mxfp8", "mca_attn_bwd_dq_fp8",
+                     "mca_attn_bwd_dkv_fp8")
+# the entry points of each form of the LAYER attention's backward, as hip.call records them (the prep launches carry no tag)
+BACKWARD_LAUNCHES = {"onepass": {"mca_attn_bwd_prep_onepass", "mca_attn_bwd_onepass/layer"},
+                     "bf16-twopass": {"mca_attn_bwd_dkv/layer", "mca_attn_bwd_dq/layer"},
+                     "fp8-twopass": {"mca_attn_quant_bwd_mxfp8/layer", "mca_attn_bwd_dkv_fp8/layer", "mca_attn_bwd_dq_fp8/layer"}}
+
+
+@pytest.mark.parametrize("size,b,dtype,onepass,plan", [
+    ("small", 6, "bf16", None, ("bf16-twopass", 1)), ("small", 6, "fp8", None, ("fp8-twopass", 1)),
+    ("cmu", 8, "bf16", None, ("onepass", 4)), ("cmu", 8, "fp8", None, ("onepass", 4)), ("cmu", 8, "fp8", False, ("fp8-twopass", 4))],
+    ids=["small-bf16", "small-fp8", "cmu-bf16", "cmu-fp8", "cmu-fp8-twopass"])
+def test_attention_backward_plan_is_what_runs(P, size, b, dtype, onepass, plan):
+    """engine.backward_plan against the launches of one training step: the layer attention's backward runs the entry points of
+    the planned form and of no other, the forward follows the operand type (fp8 operands at a batch that takes the one-pass
+    backward: fp8 forward + bf16 one-pass backward), the pooling attention is bf16 two-pass in every case."""
+    hipm = importlib.import_module("mca-paper_amd.hip")
+    cfg = small_config("mca") if size == "small" else dict(P.config.cmu_model_config(batch_size=b), depth=1)
+    torch.manual_seed(43)
+    model = P.MCA(**copy.deepcopy(cfg)).cuda()
+    eng = model.engine
+    eng.set_attention_dtype(dtype)
+    eng.dbg["onepass"] = onepass
+    batch = to_device(P.data.synthetic_batch(cfg, b, seed=5, p_drop=0.3), "cuda")
+    assert tuple(eng.backward_plan(eng.workspace(b), b, eng.N)) == plan
+    assert eng.backward_plan(eng.workspace(b), b, eng.R, dq_f32=True).form == "bf16-twopass"
+    assert eng.fp8_backward_on(eng.workspace(b), eng.N) == (plan[0] == "fp8-twopass")
+    hipm.profile_start(ATTN_ENTRY_POINTS)
+    try:
+        out = model(batch)
+        out["loss"].backward()
+    finally:
+        launched = hipm.profile_stop()
+    assert torch.isfinite(out["loss"])
+    forward = {"mca_attn_quant_mxfp8/layer", "mca_attn_fwd_fp8/layer"} if dtype == "fp8" else {"mca_attn_fwd/layer"}
+    pool = {"mca_attn_fwd/pool", "mca_attn_bwd_prep", "mca_attn_bwd_dkv/pool", "mca_attn_bwd_dq/pool"}
+    assert set(launched) == forward | pool | BACKWARD_LAUNCHES[plan[0]], sorted(launched)
+    depth = cfg["depth"]
+    assert all(launched[k][0] == depth for k in BACKWARD_LAUNCHES[plan[0]] | forward), launched
+    assert launched["mca_attn_bwd_prep"][0] == (1 if plan[0] == "onepass" else 1 + depth)          # the pooling's, and the two-pass layers'
 
 
 @pytest.mark.parametrize("kind,b", [("cmu", 32), ("mma", 32), ("tcga", 16)])

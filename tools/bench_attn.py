@@ -24,10 +24,9 @@ a = ws["layers"][0]
 a["qkv"].copy_(torch.randn_like(a["qkv"].float()).bfloat16())
 a["qkv"][:, :D] *= 0.18          # q as the engine stores it (scale * log2 e folded in)
 ws["do"].copy_(torch.randn_like(ws["do"].float()).bfloat16())
-def fwd(): eng._attn_fwd(a["qkv"].data_ptr(), N*3*D, 3*D, a["qkv"], D, 2*D, 3*D, a["o"], a["lse"], eng.qmask_attn, eng.sched_attn_f, ws, b, N)
+def fwd(): eng.attn_forward(eng.layer_attention(ws, 0)[0], ws)
 def bwd():
-    eng._attn_bwd2(a["qkv"].data_ptr(), N*3*D, 3*D, a["qkv"], D, 2*D, 3*D, a["o"], ws["do"], a["lse"], ws["delta"], a["dqkv"].data_ptr(), N*3*D, 3*D, False,
-                   a["dqkv"], D, 2*D, 3*D, eng.qmask_attn, eng.sched_attn_f, eng.sched_attn_b2, ws, b, N)
+    eng.attn_backward(*eng.layer_attention(ws, 0), ws)
 def timeit(fn, n=10):
     for _ in range(12): fn()          # (the first launches of a process touch the workspaces for the first time: 3 warm-ups left the first case 150 us high)
     torch.cuda.synchronize()

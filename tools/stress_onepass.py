@@ -30,13 +30,12 @@ for b in ((32, 16) if long_seq else (32, 8)):
         H.call("mca_build_keyhot", ws["keyinfo"].data_ptr(), ws["khot"].data_ptr(), b, eng.nk_pad, H.stream_ptr())
         a["qkv"].copy_(torch.randn(a["qkv"].shape, device="cuda", generator=g).bfloat16()); a["qkv"][:, :D] *= 0.18
         ws["do"].copy_((torch.randn(ws["do"].shape, device="cuda", generator=g) * 0.1).bfloat16())
-        eng._attn_fwd(a["qkv"].data_ptr(), N*3*D, 3*D, a["qkv"], D, 2*D, 3*D, a["o"], a["lse"], eng.qmask_attn, eng.sched_attn_f, ws, b, N)
+        eng.attn_forward(eng.layer_attention(ws, 0)[0], ws)
         outs = []
         for mode in (True, True, False):
             eng.dbg["onepass"] = mode
             a["dqkv"].fill_(7.0)
-            eng._attn_bwd2(a["qkv"].data_ptr(), N*3*D, 3*D, a["qkv"], D, 2*D, 3*D, a["o"], ws["do"], a["lse"], ws["delta"], a["dqkv"].data_ptr(), N*3*D, 3*D, False,
-                           a["dqkv"], D, 2*D, 3*D, eng.qmask_attn, eng.sched_attn_f, eng.sched_attn_b2, ws, b, N)
+            eng.attn_backward(*eng.layer_attention(ws, 0), ws)
             outs.append(a["dqkv"].clone())
         torch.cuda.synchronize()
         assert torch.equal(outs[0], outs[1]), f"b={b} round {rounds}: the one-pass backward is not repeatable"

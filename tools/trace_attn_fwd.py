@@ -15,7 +15,7 @@ a = ws["layers"][0]
 a["qkv"].copy_(torch.randn_like(a["qkv"].float()).bfloat16())
 L = H.lib(); L.mca_debug_set(8, 8)
 for _ in range(3):
-    eng._attn_fwd(a["qkv"].data_ptr(), N*3*D, 3*D, a["qkv"], D, 2*D, 3*D, a["o"], a["lse"], eng.qmask_attn, eng.sched_attn_f, ws, b, N)
+    eng.attn_forward(eng.layer_attention(ws, 0)[0], ws)
 torch.cuda.synchronize()
 buf = (C.c_ulonglong * 1024)()
 fn = L.mca_dbg_trace_read_attn_fwd; fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.c_int]

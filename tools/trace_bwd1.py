@@ -18,12 +18,11 @@ H.call("mca_build_keyhot", ws["keyinfo"].data_ptr(), ws["khot"].data_ptr(), b, e
 a = ws["layers"][0]
 a["qkv"].copy_(torch.randn_like(a["qkv"].float()).bfloat16()); a["qkv"][:, :D] *= 0.18
 ws["do"].copy_(torch.randn_like(ws["do"].float()).bfloat16())
-eng._attn_fwd(a["qkv"].data_ptr(), N*3*D, 3*D, a["qkv"], D, 2*D, 3*D, a["o"], a["lse"], eng.qmask_attn, eng.sched_attn_f, ws, b, N)
+eng.attn_forward(eng.layer_attention(ws, 0)[0], ws)
 eng.dbg["onepass"] = True
 L = H.lib(); L.mca_debug_set(9, 8)
 for _ in range(6):
-    eng._attn_bwd2(a["qkv"].data_ptr(), N*3*D, 3*D, a["qkv"], D, 2*D, 3*D, a["o"], ws["do"], a["lse"], ws["delta"], a["dqkv"].data_ptr(), N*3*D, 3*D, False,
-                   a["dqkv"], D, 2*D, 3*D, eng.qmask_attn, eng.sched_attn_f, eng.sched_attn_b2, ws, b, N)
+    eng.attn_backward(*eng.layer_attention(ws, 0), ws)
 torch.cuda.synchronize()
 buf = (C.c_ulonglong * 1024)()
 fn = L.mca_dbg_trace_read_attn_bwd1; fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.c_int]
