@@ -6,6 +6,7 @@
  */
 #ifndef MCA_HIP_DEBUG_H
 #define MCA_HIP_DEBUG_H
+#include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -29,6 +30,22 @@ extern "C" {
 int mca_debug_set(int key, int value);
 /* every knob back to 0 */
 int mca_debug_reset(void);
+
+/* Which GEMM kernel a call would launch, with which grid, LDS size and integer arguments: the planners of csrc/gemm_plan.h (where
+ * the structs are defined), as the entry points call them, with the current knob table.  cus: the CU count to plan for, 0 = ask the
+ * runtime.  Nothing is launched and no device is touched.  Return 0 or the MCA_E_* code the entry point would refuse the shape with.
+ *   mca_dbg_plan_gemm_nt        entry 0 = mca_gemm_nt, 1 = _lnres, 2 = _geglu_fwd, 3 = _geglu_bwd (the last three read M, N = ip, K only;
+ *                               kernel 0 from entry 2: the unfused pair mca_gemm_nt + mca_geglu_fwd)
+ *   mca_dbg_plan_gemm_tn        mca_gemm_tn_acc (its rule does not read the CU count)
+ *   mca_dbg_plan_gemm_tn_group  mca_gemm_tn_acc_group over n members of N[i] x K[i]: grouped or single launches, and the row partition
+ *   mca_dbg_gemm_kernel_name    the template instantiation a plan's `kernel` value stands for */
+struct mca_gemm_plan;
+struct mca_nt_problem;
+struct mca_tn_group_plan;
+int mca_dbg_plan_gemm_nt(int entry, const struct mca_nt_problem* problem, int cus, struct mca_gemm_plan* out);
+int mca_dbg_plan_gemm_tn(int64_t R, int64_t N, int64_t K, struct mca_gemm_plan* out);
+int mca_dbg_plan_gemm_tn_group(const int64_t* N, const int64_t* K, int n, int64_t R, int cus, struct mca_tn_group_plan* out);
+const char* mca_dbg_gemm_kernel_name(int kernel);
 #ifdef __cplusplus
 }
 #endif

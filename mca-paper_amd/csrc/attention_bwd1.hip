@@ -1098,14 +1098,7 @@ extern "C" int mca_attn_bwd_onepass(const mca_attn_bwd1_args* a, mca_stream_t st
   if (a->nk_pad < a->n || a->n_ktiles64 != (a->n + 63) / 64) return MCA_E_BADARG;
   if (!(a->flags & MCA_ATTN_Q_PRESCALED)) return MCA_E_UNSUPPORTED;
   if ((int64_t)a->batch * a->heads > 0x7fffffff) return MCA_E_UNSUPPORTED;
-  static bool attr_set[64] = {false};
-  bool* done = mca_dev_flag(attr_set);
-  if (!*done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd1_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, B1_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd1p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, B1P_LDS_BYTES) != hipSuccess)
-      return MCA_E_LAUNCH;
-    *done = true;
-  }
+  if (!mca_dyn_lds<attn_bwd1_kernel>(B1_LDS_BYTES) || !mca_dyn_lds<attn_bwd1p_kernel>(B1P_LDS_BYTES)) return MCA_E_LAUNCH;
   // knob 9 bit 64: the plain (compiler-scheduled) form of the same algorithm instead of the pipelined one (A/B and cross-check)
   // the pipelined kernel reads q / dO from the head-major packed copies only (64-element rows: a tile is 8 KiB contiguous)
   const bool packed = a->q_ld == DH && a->o_ld == DH && a->q_hstride && a->o_hstride;

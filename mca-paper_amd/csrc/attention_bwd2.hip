@@ -612,19 +612,14 @@ extern "C" int mca_attn_bwd_dkv(const mca_attn_bwd2_args* a, mca_stream_t stream
   if ((a->khot != nullptr) != (a->qblk != nullptr)) return MCA_E_BADARG;
   if ((uintptr_t)a->khot % 16 || (uintptr_t)a->qblk % 16) return MCA_E_ALIGN;
   if (!(a->flags & MCA_ATTN_Q_PRESCALED)) return MCA_E_UNSUPPORTED;
-  int dev = 0;
-  static bool attr_set[64] = {false};          // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device attribute
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MCA_E_LAUNCH;
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS_BYTES) != hipSuccess)
-      return MCA_E_LAUNCH;
-    attr_set[dev] = true;
-  }
   const dim3 grid(a->n_kblocks256, a->heads, a->batch);
-#define DKV_LAUNCH(W) hipLaunchKernelGGL((attn_bwd_dkv_kernel<W>), grid, dim3(64 * W), DKV_LDS_BYTES, as_stream(stream), *a, mca_knobs[9])
-  if (BKEYS == 256) DKV_LAUNCH(8); else DKV_LAUNCH(4);
-#undef DKV_LAUNCH
+  if (BKEYS == 256) {
+    if (!mca_dyn_lds<attn_bwd_dkv_kernel<8>>(DKV_LDS_BYTES)) return MCA_E_LAUNCH;
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<8>), grid, dim3(512), DKV_LDS_BYTES, as_stream(stream), *a, mca_knobs[9]);
+  } else {
+    if (!mca_dyn_lds<attn_bwd_dkv_kernel<4>>(DKV_LDS_BYTES)) return MCA_E_LAUNCH;
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<4>), grid, dim3(256), DKV_LDS_BYTES, as_stream(stream), *a, mca_knobs[9]);
+  }
   return launch_status();
 }
 

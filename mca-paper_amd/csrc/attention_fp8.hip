@@ -914,14 +914,7 @@ extern "C" int mca_attn_bwd_dkv_fp8(const mca_attn_bwd2_args* a, const mca_attn_
   if (a->nk_pad < a->n_kblocks256 * 128) return MCA_E_BADARG;
   if (a->dkv_ld % 4 || a->dkv_bstride % 4 || (uintptr_t)a->dk % 8 || (uintptr_t)a->dv % 8 || (uintptr_t)a->k_wg % 16) return MCA_E_ALIGN;
   if (a->n_qtiles64 > MAX_QTILES8) return MCA_E_UNSUPPORTED;
-  int dev = 0;
-  static bool attr_set[64] = {false};          // the attribute is per device
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MCA_E_LAUNCH;
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DKV8_LDS_BYTES) != hipSuccess)
-      return MCA_E_LAUNCH;
-    attr_set[dev] = true;
-  }
+  if (!mca_dyn_lds<attn_bwd_dkv8_kernel>(DKV8_LDS_BYTES)) return MCA_E_LAUNCH;
   hipLaunchKernelGGL(attn_bwd_dkv8_kernel, dim3(a->n_kblocks256, a->heads, a->batch), dim3(256), DKV8_LDS_BYTES, as_stream(stream), *a, *f, mca_knobs[9]);
   return launch_status();
 }

@@ -96,6 +96,18 @@ static inline bool* mca_dev_flag(bool (&flags)[64]) {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
   return &flags[dev];
 }
+// Allow KERNEL `bytes` of dynamic LDS (more than the 64 KiB a launch may ask for by default); set once per device and kernel.
+// false: the runtime refused.
+template <auto KERNEL>
+static inline bool mca_dyn_lds(int bytes) {
+  static bool done_dev[64] = {false};
+  bool* done = mca_dev_flag(done_dev);
+  if (!*done) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+    *done = true;
+  }
+  return true;
+}
 
 static inline hipStream_t as_stream(mca_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int launch_status() { return hipGetLastError() == hipSuccess ? MCA_OK : MCA_E_LAUNCH; }

@@ -20,11 +20,8 @@
 //   gemm_tn_256x256_kernel / gemm_tn_256_kernel / gemm_tn_kernel   weight gradient, split over rows + fp32 atomics
 // Workgroup ids are remapped (xcd_remap) so that workgroups sharing operands sit on one XCD / L2.
 #include "common.h"
+#include "gemm_plan.h"          // tile geometry, LDS sizes and the dispatch rules (plain host C++)
 
-#define g_knob mca_knobs     // A/B measurement knobs (mca_debug_set, optim.hip)
-
-#define BM 128
-#define BN 128
 #define BK 64
 
 static int num_cus() {
@@ -295,7 +292,6 @@ __global__ __launch_bounds__(256) void gemm_nt_glds_kernel(
 // the next stage stays in flight across the barrier (cdna guide: "Pipelining across barriers").  25 % fewer
 // global->LDS bytes per flop than the 128x128 tile.
 // ---------------------------------------------------------------------------------------------------------
-#define BM2 256
 __device__ __forceinline__ void wait_vmcnt(int n) {          // s_waitcnt needs an immediate
   switch (n) {
     case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
@@ -458,8 +454,6 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(
   }
   nt_epilogue_rows<OUT_BF16, RES, EPI, BM2, 512>(cs, Cv, ldc, bias, residual, ldres, res_period, M, N, m0, n0, tid);
 }
-#define NT256_LDS_BYTES (3 * (BM2 + BN) * 64 * 2)
-#define NT256LN_LDS_BYTES (NT256_LDS_BYTES + 2048)
 
 // ---------------------------------------------------------------------------------------------------------
 // PERSISTENT NT kernel (large M, N % 128 == 0): one 512-thread workgroup per CU walks 256x128 tiles.
@@ -493,7 +487,6 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(
 #define PS_DSW64(addr, val) asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(val) : "memory")
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
 template <int N> __device__ __forceinline__ void ps_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-#define NTPS_LDS_BYTES (3 * (BM2 + BN) * 64 * 2 + 16384)
 
 // timeline probe (TRACE build only: mca-paper_amd/build.py --trace; knob 0 = 8): workgroup 0 / wave 0 writes s_memtime stamps,
 // read back by tools/trace_persist.py; the product build carries neither the stamps nor the clock probe of the grouped kernel
@@ -801,8 +794,6 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
 // three stages are issued before the epilogue, which uses slots 3 and 4 as 8 KiB of scratch per wave (two passes of 32 rows x
 // 256 B).  vmcnt per wave: 4 loads per stage, 16 stores per tile.
 // ---------------------------------------------------------------------------------------------------------
-#define P2_STAGE (512 * 32)          // elements per stage: A image [256][32] then B image [256][32]
-#define P2_LDS_BYTES (5 * P2_STAGE * 2)
 // GEGLU = true: fused FF1 + GEGLU forward (see mca_gemm_nt_geglu_fwd): B = W1 [2*N, K] with N = ip, a column tile = 128 "a"
 // rows + the 128 "gate" rows of the same columns (wave column wn = 0 holds a, wn = 1 gate), C = h [M, 2*N], G = g [M, N].
 template <bool GEGLU>
@@ -993,194 +984,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persist256_kernel(
   }
 }
 
-extern "C" int mca_gemm_nt(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, void* C, int64_t ldc,
-                           int out_bf16, const float* bias, const float* residual, int64_t ldres,
-                           int64_t res_period, int64_t M, int64_t N, int64_t K, mca_stream_t stream) {
-  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return MCA_E_BADARG;
-  if (K % 64 || lda % 8 || ldb % 8 || (uintptr_t)A % 16 || (uintptr_t)B % 16) return MCA_E_ALIGN;
-  if (lda < K || ldb < K || ldc < N) return MCA_E_BADARG;
-  if (M > (1LL << 30) || N > (1LL << 30)) return MCA_E_UNSUPPORTED;
-  const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = (int)((N + BN - 1) / BN);
-  const int nwg = tiles_m * tiles_n;
-  const int res = !residual ? 0 : (res_period > 0 ? 2 : 1);
-  const bool big = M >= 2048 && g_knob[1] != 1;            // knob 1 = 1 forces the 128x128 kernel (A/B measurements)
-  const int nwg2 = (int)((M + BM2 - 1) / BM2) * tiles_n;
-#define NT_LAUNCH_G(OB, RS)                                                                                              \
-  hipLaunchKernelGGL((gemm_nt_glds_kernel<OB, RS, 64, 0>), dim3(nwg), dim3(256), 0, as_stream(stream), A, lda, B, ldb, C,   \
-                     ldc, bias, residual, ldres, res_period, (int)M, (int)N, (int)K, tiles_n, nwg)
-#define NT_LAUNCH_256(OB, RS, PFV)                                                                                          \
-  do {                                                                                                                   \
-    static bool attr_dev[64] = {false}; bool& attr = *mca_dev_flag(attr_dev);                                                                                            \
-    if (!attr) {                                                                                                         \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_256_kernel<OB, RS, PFV, 0>),                            \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, NT256_LDS_BYTES) != hipSuccess)                \
-        return MCA_E_LAUNCH;                                                                                             \
-      attr = true;                                                                                                       \
-    }                                                                                                                    \
-    hipLaunchKernelGGL((gemm_nt_256_kernel<OB, RS, PFV, 0>), dim3(nwg2), dim3(512), NT256_LDS_BYTES, as_stream(stream), A, lda, \
-                       B, ldb, C, ldc, bias, residual, ldres, res_period, (int)M, (int)N, (int)K, tiles_n, nwg2);        \
-  } while (0)
-#define NT_PICK_PF(OB, RS) do { if (big) NT_LAUNCH_256(OB, RS, 0); else NT_LAUNCH_G(OB, RS); } while (0)
-  // persistent kernel for bf16 / plain fp32 outputs (knob 7, A/B measurements: 1 = one-tile-per-workgroup kernels only,
-  // 3 = persistent kernel for fp32 + residual as well)
-  const bool c16 = (uintptr_t)C % 16 == 0 && ldc % (out_bf16 ? 8 : 4) == 0;
-  // (fp32 output + residual: HBM-bound, the lock-step kernel with its residual prefetch measures 10-16 % faster: MODE 2 of
-  // the persistent kernel is only used with knob 7 = 3)
-  const bool ps_res = res == 1 && !out_bf16 && ldres % 4 == 0 && (uintptr_t)residual % 16 == 0 && g_knob[7] == 3;
-  // bf16 output, N % 256 == 0: 256x256 tiles (knob 10 = 1: keep the 256x128 persistent kernel, A/B)
-  if (big && g_knob[7] == 0 && g_knob[10] != 1 && out_bf16 && res == 0 && !bias && N % 256 == 0 && K >= 192 && K % 32 == 0 && c16) {
-    static bool attr_dev[64] = {false}; bool& attr = *mca_dev_flag(attr_dev);
-    if (!attr) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_persist256_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              P2_LDS_BYTES) != hipSuccess)
-        return MCA_E_LAUNCH;
-      attr = true;
-    }
-    const int tn2 = (int)(N / 256), nw2 = (int)((M + 255) / 256) * tn2;
-    const int grid = nw2 < num_cus() ? nw2 : num_cus();
-    hipLaunchKernelGGL(gemm_nt_persist256_kernel<false>, dim3(grid), dim3(512), P2_LDS_BYTES, as_stream(stream), A, lda, B, ldb,
-                       reinterpret_cast<u16*>(C), ldc, (u16*)nullptr, (int64_t)0, (int)M, (int)N, (int)K, tn2, nw2, g_knob[0]);
-    return launch_status();
-  }
-  if (big && (g_knob[7] == 0 || g_knob[7] == 3) && N % BN == 0 && K >= 320 && c16 && (res == 0 || ps_res) && (!bias || (uintptr_t)bias % 16 == 0)) {
-    const int grid = nwg2 < num_cus() ? nwg2 : num_cus();
-#define NT_LAUNCH_PS(MODE, BI)                                                                                               \
-  do {                                                                                                                   \
-    static bool attr_dev[64] = {false}; bool& attr = *mca_dev_flag(attr_dev);                                                                                            \
-    if (!attr) {                                                                                                         \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_persist_kernel<MODE, BI>),                           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, NTPS_LDS_BYTES) != hipSuccess)                 \
-        return MCA_E_LAUNCH;                                                                                             \
-      attr = true;                                                                                                       \
-    }                                                                                                                    \
-    hipLaunchKernelGGL((gemm_nt_persist_kernel<MODE, BI>), dim3(grid), dim3(512), NTPS_LDS_BYTES, as_stream(stream), A, lda, B, \
-                       ldb, C, ldc, bias, residual, ldres, (int)M, (int)N, (int)K, tiles_n, nwg2, g_knob[0]);            \
-  } while (0)
-    if (out_bf16) { if (bias) NT_LAUNCH_PS(0, true); else NT_LAUNCH_PS(0, false); }
-    else if (res == 0) { if (bias) NT_LAUNCH_PS(1, true); else NT_LAUNCH_PS(1, false); }
-    else { if (bias) NT_LAUNCH_PS(2, true); else NT_LAUNCH_PS(2, false); }
-    return launch_status();
-  }
-  const bool pf = big && !out_bf16 && res == 1 && N % BN == 0 && K >= 512 && ldres % 4 == 0 && ldc % 4 == 0 &&
-                  (uintptr_t)residual % 16 == 0 && (uintptr_t)C % 16 == 0 && (!bias || (uintptr_t)bias % 4 == 0) && g_knob[4] != 1;
-  if (pf) { NT_LAUNCH_256(false, 1, 1); return launch_status(); }
-  if (out_bf16) { if (res == 0) NT_PICK_PF(true, 0); else if (res == 1) NT_PICK_PF(true, 1); else NT_PICK_PF(true, 2); }
-  else { if (res == 0) NT_PICK_PF(false, 0); else if (res == 1) NT_PICK_PF(false, 1); else NT_PICK_PF(false, 2); }
-  return launch_status();
-}
-
-
-// C[M,N] (fp32) = A·B^T + LayerNorm(x) with the LayerNorm recomputed in the epilogue from x and its saved statistics.
-extern "C" int mca_gemm_nt_lnres(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, float* C, int64_t ldc,
-                                 const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
-                                 int64_t M, int64_t N, int64_t K, mca_stream_t stream) {
-  if (!A || !B || !C || !x || !mean || !rstd || !gamma || M <= 0 || N <= 0 || K <= 0) return MCA_E_BADARG;
-  if (K % 64 || lda % 8 || ldb % 8 || ldc % 4 || ldx % 4 || (uintptr_t)A % 16 || (uintptr_t)B % 16 || (uintptr_t)C % 16 ||
-      (uintptr_t)x % 16 || (uintptr_t)gamma % 16)
-    return MCA_E_ALIGN;
-  if (lda < K || ldb < K || ldc < N || ldx < N) return MCA_E_BADARG;
-  // the fused form exists for the large-M residual-prefetch kernel only; callers keep the two-kernel form otherwise
-  if (M < 2048 || M > (1LL << 30) || N % BN || K < 512) return MCA_E_UNSUPPORTED;
-  const int tiles_n = (int)(N / BN);
-  const int nwg2 = (int)((M + BM2 - 1) / BM2) * tiles_n;
-  static bool attr_dev[64] = {false}; bool& attr = *mca_dev_flag(attr_dev);
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_256_kernel<false, 1, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            NT256LN_LDS_BYTES) != hipSuccess)
-      return MCA_E_LAUNCH;
-    attr = true;
-  }
-  hipLaunchKernelGGL((gemm_nt_256_kernel<false, 1, 1, 2>), dim3(nwg2), dim3(512), NT256LN_LDS_BYTES, as_stream(stream), A, lda, B, ldb,
-                     (void*)C, ldc, (const float*)nullptr, x, ldx, (int64_t)0, (int)M, (int)N, (int)K, tiles_n, nwg2, mean, rstd, gamma);
-  return launch_status();
-}
-
-// dh = GEGLU'(h) applied to dg = A·B^T without materialising dg (fused epilogue).  A[M,K] (= d x_out, bf16), B[ip,K] (= W2^T
-// copy), h / dh [M, 2*ip] bf16.
-extern "C" int mca_gemm_nt_geglu_bwd(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const uint16_t* h,
-                                     uint16_t* dh, int64_t ldh, int64_t ip, int64_t M, int64_t K, mca_stream_t stream) {
-  if (!A || !B || !h || !dh || M <= 0 || ip <= 0 || K <= 0) return MCA_E_BADARG;
-  if (K % 64 || lda % 8 || ldb % 8 || ldh % 8 || ip % 8 || (uintptr_t)A % 16 || (uintptr_t)B % 16 || (uintptr_t)h % 16 || (uintptr_t)dh % 16)
-    return MCA_E_ALIGN;
-  if (lda < K || ldb < K || ldh < 2 * ip) return MCA_E_BADARG;
-  if (M > (1LL << 30)) return MCA_E_UNSUPPORTED;
-  const int64_t N = ip;
-  const int tiles_n = (int)((N + BN - 1) / BN);
-  const float* hres = reinterpret_cast<const float*>(h);
-  void* C = dh;
-  // below ~40k rows (the data-parallel configs' 8 samples per GPU: 20,304 rows) the 128 x 128 kernel, two or three workgroups
-  // per CU whose epilogues (0.9 GB of h / dh traffic at b = 32) overlap each other's k-loops, beats the persistent 256 x 128
-  // one (65 against 75 us at b = 8; 308 against 282 at b = 32: tools/bench_step_gemms.py); knob 1 = 1 forces it (A/B)
-  if (M >= 40960 && g_knob[1] != 1) {
-    const int nwg2 = (int)((M + BM2 - 1) / BM2) * tiles_n;
-    static bool attr_dev[64] = {false}; bool& attr = *mca_dev_flag(attr_dev);
-    if (!attr) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_256_kernel<true, 0, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              NT256_LDS_BYTES) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_persist_kernel<3, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              NTPS_LDS_BYTES) != hipSuccess)
-        return MCA_E_LAUNCH;
-      attr = true;
-    }
-    if (g_knob[7] != 1 && N % BN == 0 && K >= 320) {
-      const int grid = nwg2 < num_cus() ? nwg2 : num_cus();
-      hipLaunchKernelGGL((gemm_nt_persist_kernel<3, false>), dim3(grid), dim3(512), NTPS_LDS_BYTES, as_stream(stream), A, lda, B, ldb, C, ldh,
-                         nullptr, hres, ldh, (int)M, (int)N, (int)K, tiles_n, nwg2, g_knob[0]);
-    } else
-      hipLaunchKernelGGL((gemm_nt_256_kernel<true, 0, 0, 1>), dim3(nwg2), dim3(512), NT256_LDS_BYTES, as_stream(stream), A, lda, B, ldb, C,
-                         ldh, nullptr, hres, ldh, 0, (int)M, (int)N, (int)K, tiles_n, nwg2);
-  } else {
-    const int nwg = (int)((M + BM - 1) / BM) * tiles_n;
-    hipLaunchKernelGGL((gemm_nt_glds_kernel<true, 0, 64, 1>), dim3(nwg), dim3(256), 0, as_stream(stream), A, lda, B, ldb, C, ldh, nullptr,
-                       hres, ldh, 0, (int)M, (int)N, (int)K, tiles_n, nwg);
-  }
-  return launch_status();
-}
-
-// h = A·W1^T (bf16, [a | gate]) and g = a * gelu(gate) in one pass (persistent kernel MODE 4); small or oddly shaped
-// problems take the plain GEMM followed by the element-wise kernel.
-extern "C" int mca_gemm_nt_geglu_fwd(const uint16_t* A, int64_t lda, const uint16_t* W1, int64_t ldb, uint16_t* h, int64_t ldh,
-                                     uint16_t* g, int64_t ldg, int64_t ip, int64_t M, int64_t K, mca_stream_t stream) {
-  if (!A || !W1 || !h || !g || M <= 0 || ip <= 0 || K <= 0) return MCA_E_BADARG;
-  if (K % 64 || lda % 8 || ldb % 8 || ldh % 8 || ldg % 8 || ip % 8 || (uintptr_t)A % 16 || (uintptr_t)W1 % 16 || (uintptr_t)h % 16 ||
-      (uintptr_t)g % 16)
-    return MCA_E_ALIGN;
-  if (lda < K || ldb < K || ldh < 2 * ip || ldg < ip) return MCA_E_BADARG;
-  if (M > (1LL << 30)) return MCA_E_UNSUPPORTED;
-  if (M >= 2048 && ip % 128 == 0 && K >= 192 && g_knob[7] != 1 && g_knob[10] != 1) {
-    static bool attr2_dev[64] = {false}; bool& attr2 = *mca_dev_flag(attr2_dev);
-    if (!attr2) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_persist256_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              P2_LDS_BYTES) != hipSuccess)
-        return MCA_E_LAUNCH;
-      attr2 = true;
-    }
-    const int tn2 = (int)(ip / 128), nw2 = (int)((M + 255) / 256) * tn2;
-    const int grid = nw2 < num_cus() ? nw2 : num_cus();
-    hipLaunchKernelGGL(gemm_nt_persist256_kernel<true>, dim3(grid), dim3(512), P2_LDS_BYTES, as_stream(stream), A, lda, W1, ldb, h, ldh, g,
-                       ldg, (int)M, (int)ip, (int)K, tn2, nw2, g_knob[0]);
-    return launch_status();
-  }
-  if (M >= 2048 && ip % 64 == 0 && K >= 320 && g_knob[7] != 1) {
-    static bool attr_dev[64] = {false}; bool& attr = *mca_dev_flag(attr_dev);
-    if (!attr) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_persist_kernel<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              NTPS_LDS_BYTES) != hipSuccess)
-        return MCA_E_LAUNCH;
-      attr = true;
-    }
-    const int tiles_n = (int)(ip / 64);
-    const int nwg2 = (int)((M + BM2 - 1) / BM2) * tiles_n;
-    const int grid = nwg2 < num_cus() ? nwg2 : num_cus();
-    hipLaunchKernelGGL((gemm_nt_persist_kernel<4, false>), dim3(grid), dim3(512), NTPS_LDS_BYTES, as_stream(stream), A, lda, W1, ldb, h, ldh,
-                       nullptr, reinterpret_cast<const float*>(g), ldg, (int)M, (int)ip, (int)K, tiles_n, nwg2, g_knob[0]);
-    return launch_status();
-  }
-  if (ldg != ip || ldh != 2 * ip) return MCA_E_UNSUPPORTED;          // the element-wise kernel takes packed rows
-  const int rc = mca_gemm_nt(A, lda, W1, ldb, h, ldh, 1, nullptr, nullptr, 0, 0, M, 2 * ip, K, stream);
-  if (rc != MCA_OK) return rc;
-  return mca_geglu_fwd(h, g, M, (int)ip, stream);
-}
+// (the entry points of these kernels: end of file, after the weight-gradient kernels)
 
 // =====================================================================================================
 // weight gradient:  C[N,K] += A[R,N]^T · B[R,K]
@@ -1188,10 +992,26 @@ extern "C" int mca_gemm_nt_geglu_fwd(const uint16_t* A, int64_t lda, const uint1
 // c ^ (4*(r & 3)): the four rows of one transposed 4x16 read then sit in four different 64-byte bank
 // quarters (conflict-free ds_read_b64_tr_b16).
 // =====================================================================================================
-#define BR 64
 __device__ __forceinline__ int tn_off(int r, int c) { return r * 128 + ((c ^ ((r & 3) << 2)) << 3); }
 
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
+
+// fragment fetch by the transposed LDS read, and one parity's MFMA group (fa / fb / acc of the enclosing k-loop): shared by
+// the 128 x 128 and 256 x 128 kernels, TR_READ by the 256 x 256 one as well
+#define TR_READ(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
+#define TN_MFMA(PAR)                                                             \
+  {                                                                            \
+    bf16x8 af[2], bfr[2];                                                      \
+    _Pragma("unroll") for (int i = 0; i < 2; i++) {                            \
+      const uint4 ua = make_uint4(fa[PAR][i][0][0], fa[PAR][i][0][1], fa[PAR][i][1][0], fa[PAR][i][1][1]); \
+      const uint4 ub = make_uint4(fb[PAR][i][0][0], fb[PAR][i][0][1], fb[PAR][i][1][0], fb[PAR][i][1][1]); \
+      af[i] = *reinterpret_cast<const bf16x8*>(&ua);                           \
+      bfr[i] = *reinterpret_cast<const bf16x8*>(&ub);                          \
+    }                                                                          \
+    _Pragma("unroll") for (int i = 0; i < 2; i++)                              \
+      _Pragma("unroll") for (int j = 0; j < 2; j++)                            \
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0); \
+  }
 
 __global__ __launch_bounds__(256) void gemm_tn_kernel(const u16* __restrict__ A, int64_t lda,
                                                        const u16* __restrict__ B, int64_t ldb, float* __restrict__ C,
@@ -1263,7 +1083,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const u16* __restrict__ A,
     }
   }
   typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-#define TR_READ(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
   const int nsteps = (r_end - r_begin + BR - 1) / BR;
   stage(r_begin, 0);
   __syncthreads();
@@ -1278,19 +1097,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const u16* __restrict__ A,
     TR_READ(fa[PAR][1][0], a1, (KS) * 4096); TR_READ(fa[PAR][1][1], a1, (KS) * 4096 + 1024); \
     TR_READ(fb[PAR][0][0], b0, (KS) * 4096); TR_READ(fb[PAR][0][1], b0, (KS) * 4096 + 1024); \
     TR_READ(fb[PAR][1][0], b1, (KS) * 4096); TR_READ(fb[PAR][1][1], b1, (KS) * 4096 + 1024);
-#define TN_MFMA(PAR)                                                             \
-    {                                                                            \
-      bf16x8 af[2], bfr[2];                                                      \
-      _Pragma("unroll") for (int i = 0; i < 2; i++) {                            \
-        const uint4 ua = make_uint4(fa[PAR][i][0][0], fa[PAR][i][0][1], fa[PAR][i][1][0], fa[PAR][i][1][1]); \
-        const uint4 ub = make_uint4(fb[PAR][i][0][0], fb[PAR][i][0][1], fb[PAR][i][1][0], fb[PAR][i][1][1]); \
-        af[i] = *reinterpret_cast<const bf16x8*>(&ua);                           \
-        bfr[i] = *reinterpret_cast<const bf16x8*>(&ub);                          \
-      }                                                                          \
-      _Pragma("unroll") for (int i = 0; i < 2; i++)                              \
-        _Pragma("unroll") for (int j = 0; j < 2; j++)                            \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0); \
-    }
     TN_ISSUE(0, 0)
     TN_ISSUE(1, 1)
     asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
@@ -1308,8 +1114,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const u16* __restrict__ A,
     __syncthreads();
   }
 #undef TN_ISSUE
-#undef TN_MFMA
-#undef TR_READ
   // C[n][k]: row n in registers, column k on the lane -> 128-byte contiguous atomic segments per row
   const int l31 = lane & 31;
 #pragma unroll
@@ -1407,7 +1211,6 @@ __global__ __launch_bounds__(512) void gemm_tn_256_kernel(const u16* __restrict_
     }
   }
   typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-#define TR_READ(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
   const int nsteps = (r_end - r_begin + BR - 1) / BR;
   stage(r_begin, 0);
   if (nsteps > 1) stage(r_begin + BR, 1);
@@ -1425,19 +1228,6 @@ __global__ __launch_bounds__(512) void gemm_tn_256_kernel(const u16* __restrict_
     TR_READ(fa[PAR][1][0], a1, (KS) * 8192); TR_READ(fa[PAR][1][1], a1, (KS) * 8192 + 2048); \
     TR_READ(fb[PAR][0][0], b0, (KS) * 4096); TR_READ(fb[PAR][0][1], b0, (KS) * 4096 + 1024); \
     TR_READ(fb[PAR][1][0], b1, (KS) * 4096); TR_READ(fb[PAR][1][1], b1, (KS) * 4096 + 1024);
-#define TN_MFMA(PAR)                                                             \
-    {                                                                            \
-      bf16x8 af[2], bfr[2];                                                      \
-      _Pragma("unroll") for (int i = 0; i < 2; i++) {                            \
-        const uint4 ua = make_uint4(fa[PAR][i][0][0], fa[PAR][i][0][1], fa[PAR][i][1][0], fa[PAR][i][1][1]); \
-        const uint4 ub = make_uint4(fb[PAR][i][0][0], fb[PAR][i][0][1], fb[PAR][i][1][0], fb[PAR][i][1][1]); \
-        af[i] = *reinterpret_cast<const bf16x8*>(&ua);                           \
-        bfr[i] = *reinterpret_cast<const bf16x8*>(&ub);                          \
-      }                                                                          \
-      _Pragma("unroll") for (int i = 0; i < 2; i++)                              \
-        _Pragma("unroll") for (int j = 0; j < 2; j++)                            \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0); \
-    }
     TN_ISSUE(0, 0)
     TN_ISSUE(1, 1)
     asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
@@ -1456,7 +1246,6 @@ __global__ __launch_bounds__(512) void gemm_tn_256_kernel(const u16* __restrict_
   }
 #undef TN_ISSUE
 #undef TN_MFMA
-#undef TR_READ
   const int l31 = lane & 31;
 #pragma unroll
   for (int j = 0; j < 2; j++) {
@@ -1471,7 +1260,6 @@ __global__ __launch_bounds__(512) void gemm_tn_256_kernel(const u16* __restrict_
       }
   }
 }
-#define TN256_LDS_BYTES (3 * BR * (256 + 128) * 2)
 
 // ---------------------------------------------------------------------------------------------------------
 // Weight gradient, 256(n) x 256(k) output tile: the k-loop of these GEMMs is bound by the L2 -> LDS path per CU
@@ -1480,10 +1268,6 @@ __global__ __launch_bounds__(512) void gemm_tn_256_kernel(const u16* __restrict_
 // 256x128.  8 wavefronts as 4 (n) x 2 (k), each 64 x 128 = 2 x 4 accumulators (128 VGPRs); FIVE LDS stages of
 // 32 rows (160 KiB), DMA four steps ahead; fragments by ds_read_b64_tr_b16 (12 per k16-step for 8 MFMAs).
 // ---------------------------------------------------------------------------------------------------------
-#define BR2 32
-#define TN2_STAGE (BR2 * 512)          // elements per stage: A image [32][256] then B image [32][256]
-#define TN2_NSTAGE 5
-#define TN2_LDS_BYTES (TN2_NSTAGE * TN2_STAGE * 2)
 __device__ __forceinline__ void tn_256x256_tile(const u16* __restrict__ A, int64_t lda, const u16* __restrict__ B, int64_t ldb,
                                                 float* __restrict__ C, int64_t ldc, int N, int K, int tn, int tk, int r_begin,
                                                 int r_end, u16* ldst) {
@@ -1555,7 +1339,6 @@ __device__ __forceinline__ void tn_256x256_tile(const u16* __restrict__ A, int64
     }
   }
   typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-#define TR_READ(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
   // FIVE stages of 32 rows (all 160 KiB of LDS), DMA four steps ahead.  The step is software-pipelined: the fragments of one
   // k16-step are read in the gaps between the MFMAs of the k16-step before it (two reads per gap, none in a burst), and the step's
   // one barrier sits between its two MFMA groups, followed by one MFMA before the next stage's DMA is issued.
@@ -1650,7 +1433,6 @@ __global__ __launch_bounds__(512) void gemm_tn_256x256_kernel(const u16* __restr
 // Several weight gradients over the SAME token rows in one launch (the four of a transformer layer): the launch then has
 // 48 tiles instead of 12, so a full round of workgroups needs 5 row splits instead of 21 and the fp32 atomic traffic (every
 // split adds the whole gradient once; a quarter to a third of the single launches' time) drops four-fold.
-#define TN_SPAN_RELIEF 1536       // rows a two-tile workgroup is relieved of (mca_gemm_tn_acc_group; measured: tools/bench_tn_group.py)
 struct tn_group {
   const u16* A[MCA_TN_MAX_GROUP];
   const u16* B[MCA_TN_MAX_GROUP];
@@ -1659,17 +1441,7 @@ struct tn_group {
   int N[MCA_TN_MAX_GROUP], K[MCA_TN_MAX_GROUP], tiles_k[MCA_TN_MAX_GROUP];
   int first_tile[MCA_TN_MAX_GROUP + 1];
   int n, R, tiles;
-  // Balanced row partition: every workgroup reduces `unit` rows of one tile's worth of work.  The first n_full * tiles
-  // workgroups take whole (tile, split) cells of `unit` rows as before (the tiles of one split next to each other on an XCD, so
-  // that an operand row block is fetched into one L2 once); the rows left over, [n_full * unit, R) of every tile, form a second,
-  // tile-major line of tiles * (R - n_full * unit) row-units that the remaining workgroups cut into equal spans of `span` rows (a little less than `unit`): such a
-  // workgroup finishes one tile's rest and starts the next one's (two atomic epilogues).  Any number of tiles then fills the
-  // chip's one round of workgroups: 52 tiles are 4 full splits on 208 CUs + 48 spans, not 4 splits with 48 CUs idle (worth 7 % at
-  // b = 32, not 19 %: the launch is bound by the shared L2 -> LDS and atomic paths, tools/bench_tn_group.py).
-  int unit, n_full, span;          // rows of a whole cell, cells per tile, rows of a span of the line
-  // own > 0 (when the line's workgroups are at least half as many as the tiles): the first `own` of them each take the whole
-  // rest of "their" tile first - rows [n_full * unit, R) of tiles 0 .. own - 1, the SAME rows at the same time, so these segments
-  // share operand rows through L2 like the cells do - and only tiles own .. tiles - 1 form the line (spans of `span` rows)
+  int unit, n_full, span;          // the balanced row partition: mca_tn_partition (gemm_plan.h), planned by mca_plan_gemm_tn_group
   int own;
 };
 __global__ __launch_bounds__(512) void gemm_tn_256x256_group_kernel(tn_group g, int dbg) {
@@ -1680,6 +1452,8 @@ __global__ __launch_bounds__(512) void gemm_tn_256x256_group_kernel(tn_group g, 
   const bool probe = (dbg & 8) && threadIdx.x == 0 && lin0 < 512;
   const uint64_t c0 = probe ? __builtin_amdgcn_s_memtime() : 0, t0 = probe ? __builtin_amdgcn_s_memrealtime() : 0;
 #endif
+  // (the segment arithmetic below has a line-for-line host copy, mca_tn_group_segments in gemm_plan.h, which the CPU tests run:
+  //  change both or neither)
   const int n_cells = g.n_full * g.tiles;
   const int row0 = g.n_full * g.unit, rest = g.R - row0;          // rows [row0, R) of every tile
   // this workgroup's span [s, e) of the tile-major line over tiles line0 .. tiles - 1 (a whole cell is the degenerate case: one
@@ -1730,81 +1504,189 @@ __global__ __launch_bounds__(512) void gemm_tn_256x256_group_kernel(tn_group g, 
 #endif
 }
 
-extern "C" int mca_gemm_tn_acc(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, float* C, int64_t ldc,
-                               int64_t R, int64_t N, int64_t K, mca_stream_t stream) {
-  if (!A || !B || !C || R <= 0 || N <= 0 || K <= 0) return MCA_E_BADARG;
+// =====================================================================================================
+// Entry points: validate, plan (gemm_plan.h), launch what the plan says.
+// =====================================================================================================
+struct gemm_operands {
+  const u16* A; int64_t lda;
+  const u16* B; int64_t ldb;
+  void* C; int64_t ldc;
+  const float* bias;
+  const float* residual; int64_t ldres, res_period;          // the GEGLU fusions pass h (backward) / g (forward) here
+  const float *ln_mean, *ln_rstd, *ln_gamma;
+  int M, K;                                                  // (weight gradient: M = R, the rows reduced)
+  const tn_group* group;
+};
+
+template <auto KERNEL, typename... Args>
+static int launch_kernel(const mca_gemm_plan& p, mca_stream_t stream, Args... args) {
+  if (p.lds_bytes && !mca_dyn_lds<KERNEL>(p.lds_bytes)) return MCA_E_LAUNCH;
+  hipLaunchKernelGGL(KERNEL, dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds_bytes, as_stream(stream), args...);
+  return launch_status();
+}
+// the four argument lists of the NT kernels, and the weight gradient's
+template <bool OB, int RS, int EPI>
+static int launch_glds(const mca_gemm_plan& p, const gemm_operands& o, mca_stream_t s) {
+  return launch_kernel<gemm_nt_glds_kernel<OB, RS, 64, EPI>>(p, s, o.A, o.lda, o.B, o.ldb, o.C, o.ldc, o.bias, o.residual, o.ldres, o.res_period,
+                                                             o.M, p.n, o.K, p.tiles_n, p.nwg);
+}
+template <bool OB, int RS, int PF, int EPI>
+static int launch_256(const mca_gemm_plan& p, const gemm_operands& o, mca_stream_t s) {
+  return launch_kernel<gemm_nt_256_kernel<OB, RS, PF, EPI>>(p, s, o.A, o.lda, o.B, o.ldb, o.C, o.ldc, o.bias, o.residual, o.ldres, o.res_period,
+                                                            o.M, p.n, o.K, p.tiles_n, p.nwg, o.ln_mean, o.ln_rstd, o.ln_gamma);
+}
+template <int MODE, bool BIAS>
+static int launch_persist(const mca_gemm_plan& p, const gemm_operands& o, mca_stream_t s) {
+  return launch_kernel<gemm_nt_persist_kernel<MODE, BIAS>>(p, s, o.A, o.lda, o.B, o.ldb, o.C, o.ldc, o.bias, o.residual, o.ldres, o.M, p.n, o.K,
+                                                           p.tiles_n, p.nwg, p.dbg);
+}
+template <bool GEGLU>
+static int launch_persist256(const mca_gemm_plan& p, const gemm_operands& o, mca_stream_t s) {
+  u16* g = GEGLU ? reinterpret_cast<u16*>(const_cast<float*>(o.residual)) : nullptr;
+  return launch_kernel<gemm_nt_persist256_kernel<GEGLU>>(p, s, o.A, o.lda, o.B, o.ldb, reinterpret_cast<u16*>(o.C), o.ldc, g,
+                                                         GEGLU ? o.ldres : (int64_t)0, o.M, p.n, o.K, p.tiles_n, p.nwg, p.dbg);
+}
+template <auto KERNEL>
+static int launch_tn(const mca_gemm_plan& p, const gemm_operands& o, mca_stream_t s) {
+  return launch_kernel<KERNEL>(p, s, o.A, o.lda, o.B, o.ldb, reinterpret_cast<float*>(o.C), o.ldc, o.M, p.n, o.K, p.tiles_k, p.rows_per_split, p.dbg);
+}
+
+static int launch(const mca_gemm_plan& p, const gemm_operands& o, mca_stream_t s) {
+  switch (p.kernel) {
+    case MCA_GK_NT_GLDS + 0: return launch_glds<false, 0, 0>(p, o, s);
+    case MCA_GK_NT_GLDS + 1: return launch_glds<false, 1, 0>(p, o, s);
+    case MCA_GK_NT_GLDS + 2: return launch_glds<false, 2, 0>(p, o, s);
+    case MCA_GK_NT_GLDS + 3: return launch_glds<true, 0, 0>(p, o, s);
+    case MCA_GK_NT_GLDS + 4: return launch_glds<true, 1, 0>(p, o, s);
+    case MCA_GK_NT_GLDS + 5: return launch_glds<true, 2, 0>(p, o, s);
+    case MCA_GK_NT_GLDS_GEGLU_BWD: return launch_glds<true, 0, 1>(p, o, s);
+    case MCA_GK_NT_256 + 0: return launch_256<false, 0, 0, 0>(p, o, s);
+    case MCA_GK_NT_256 + 1: return launch_256<false, 1, 0, 0>(p, o, s);
+    case MCA_GK_NT_256 + 2: return launch_256<false, 2, 0, 0>(p, o, s);
+    case MCA_GK_NT_256 + 3: return launch_256<true, 0, 0, 0>(p, o, s);
+    case MCA_GK_NT_256 + 4: return launch_256<true, 1, 0, 0>(p, o, s);
+    case MCA_GK_NT_256 + 5: return launch_256<true, 2, 0, 0>(p, o, s);
+    case MCA_GK_NT_256_PF: return launch_256<false, 1, 1, 0>(p, o, s);
+    case MCA_GK_NT_256_LNRES: return launch_256<false, 1, 1, 2>(p, o, s);
+    case MCA_GK_NT_256_GEGLU_BWD: return launch_256<true, 0, 0, 1>(p, o, s);
+    case MCA_GK_NT_PERSIST + 0: return launch_persist<0, false>(p, o, s);
+    case MCA_GK_NT_PERSIST + 1: return launch_persist<0, true>(p, o, s);
+    case MCA_GK_NT_PERSIST + 2: return launch_persist<1, false>(p, o, s);
+    case MCA_GK_NT_PERSIST + 3: return launch_persist<1, true>(p, o, s);
+    case MCA_GK_NT_PERSIST + 4: return launch_persist<2, false>(p, o, s);
+    case MCA_GK_NT_PERSIST + 5: return launch_persist<2, true>(p, o, s);
+    case MCA_GK_NT_PERSIST_GEGLU_BWD: return launch_persist<3, false>(p, o, s);
+    case MCA_GK_NT_PERSIST_GEGLU_FWD: return launch_persist<4, false>(p, o, s);
+    case MCA_GK_NT_PERSIST256: return launch_persist256<false>(p, o, s);
+    case MCA_GK_NT_PERSIST256_GEGLU_FWD: return launch_persist256<true>(p, o, s);
+    case MCA_GK_TN: return launch_tn<gemm_tn_kernel>(p, o, s);
+    case MCA_GK_TN_256: return launch_tn<gemm_tn_256_kernel>(p, o, s);
+    case MCA_GK_TN_256X256: return launch_tn<gemm_tn_256x256_kernel>(p, o, s);
+    case MCA_GK_TN_256X256_GROUP: return launch_kernel<gemm_tn_256x256_group_kernel>(p, s, *o.group, p.dbg);
+  }
+  return MCA_E_LAUNCH;          // a plan without a kernel is a missing kernel, never a quiet no-op
+}
+
+static uint64_t addr(const void* p) { return (uint64_t)(uintptr_t)p; }
+
+extern "C" int mca_gemm_nt(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, void* C, int64_t ldc,
+                           int out_bf16, const float* bias, const float* residual, int64_t ldres,
+                           int64_t res_period, int64_t M, int64_t N, int64_t K, mca_stream_t stream) {
+  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return MCA_E_BADARG;
+  if (K % 64 || lda % 8 || ldb % 8 || (uintptr_t)A % 16 || (uintptr_t)B % 16) return MCA_E_ALIGN;
+  if (lda < K || ldb < K || ldc < N) return MCA_E_BADARG;
+  if (M > (1LL << 30) || N > (1LL << 30)) return MCA_E_UNSUPPORTED;
+  const mca_nt_problem pr = {M, N, K, out_bf16, res_period, addr(C), addr(bias), addr(residual), ldc, ldres};
+  const gemm_operands o = {A, lda, B, ldb, C, ldc, bias, residual, ldres, res_period, nullptr, nullptr, nullptr, (int)M, (int)K, nullptr};
+  return launch(mca_plan_gemm_nt(pr, mca_knobs, num_cus()), o, stream);
+}
+
+// C[M,N] (fp32) = A·B^T + LayerNorm(x) with the LayerNorm recomputed in the epilogue from x and its saved statistics.
+extern "C" int mca_gemm_nt_lnres(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, float* C, int64_t ldc,
+                                 const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
+                                 int64_t M, int64_t N, int64_t K, mca_stream_t stream) {
+  if (!A || !B || !C || !x || !mean || !rstd || !gamma || M <= 0 || N <= 0 || K <= 0) return MCA_E_BADARG;
+  if (K % 64 || lda % 8 || ldb % 8 || ldc % 4 || ldx % 4 || (uintptr_t)A % 16 || (uintptr_t)B % 16 || (uintptr_t)C % 16 ||
+      (uintptr_t)x % 16 || (uintptr_t)gamma % 16)
+    return MCA_E_ALIGN;
+  if (lda < K || ldb < K || ldc < N || ldx < N) return MCA_E_BADARG;
+  if (!mca_nt_lnres_supported(M, N, K)) return MCA_E_UNSUPPORTED;
+  const gemm_operands o = {A, lda, B, ldb, C, ldc, nullptr, x, ldx, 0, mean, rstd, gamma, (int)M, (int)K, nullptr};
+  return launch(mca_plan_gemm_nt_lnres(M, N), o, stream);
+}
+
+// dh = GEGLU'(h) applied to dg = A·B^T without materialising dg (fused epilogue).  A[M,K] (= d x_out, bf16), B[ip,K] (= W2^T
+// copy), h / dh [M, 2*ip] bf16.
+extern "C" int mca_gemm_nt_geglu_bwd(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const uint16_t* h,
+                                     uint16_t* dh, int64_t ldh, int64_t ip, int64_t M, int64_t K, mca_stream_t stream) {
+  if (!A || !B || !h || !dh || M <= 0 || ip <= 0 || K <= 0) return MCA_E_BADARG;
+  if (K % 64 || lda % 8 || ldb % 8 || ldh % 8 || ip % 8 || (uintptr_t)A % 16 || (uintptr_t)B % 16 || (uintptr_t)h % 16 || (uintptr_t)dh % 16)
+    return MCA_E_ALIGN;
+  if (lda < K || ldb < K || ldh < 2 * ip) return MCA_E_BADARG;
+  if (M > (1LL << 30)) return MCA_E_UNSUPPORTED;
+  const gemm_operands o = {A, lda, B, ldb, dh, ldh, nullptr, reinterpret_cast<const float*>(h), ldh, 0, nullptr, nullptr, nullptr, (int)M, (int)K, nullptr};
+  return launch(mca_plan_gemm_nt_geglu_bwd(M, ip, K, mca_knobs, num_cus()), o, stream);
+}
+
+// h = A·W1^T (bf16, [a | gate]) and g = a * gelu(gate) in one pass (persistent kernels); small or oddly shaped
+// problems take the plain GEMM followed by the element-wise kernel.
+extern "C" int mca_gemm_nt_geglu_fwd(const uint16_t* A, int64_t lda, const uint16_t* W1, int64_t ldb, uint16_t* h, int64_t ldh,
+                                     uint16_t* g, int64_t ldg, int64_t ip, int64_t M, int64_t K, mca_stream_t stream) {
+  if (!A || !W1 || !h || !g || M <= 0 || ip <= 0 || K <= 0) return MCA_E_BADARG;
+  if (K % 64 || lda % 8 || ldb % 8 || ldh % 8 || ldg % 8 || ip % 8 || (uintptr_t)A % 16 || (uintptr_t)W1 % 16 || (uintptr_t)h % 16 ||
+      (uintptr_t)g % 16)
+    return MCA_E_ALIGN;
+  if (lda < K || ldb < K || ldh < 2 * ip || ldg < ip) return MCA_E_BADARG;
+  if (M > (1LL << 30)) return MCA_E_UNSUPPORTED;
+  const mca_gemm_plan p = mca_plan_gemm_nt_geglu_fwd(M, ip, K, mca_knobs, num_cus());
+  if (p.kernel != MCA_GK_NONE) {
+    const gemm_operands o = {A, lda, W1, ldb, h, ldh, nullptr, reinterpret_cast<const float*>(g), ldg, 0, nullptr, nullptr, nullptr, (int)M, (int)K, nullptr};
+    return launch(p, o, stream);
+  }
+  if (ldg != ip || ldh != 2 * ip) return MCA_E_UNSUPPORTED;          // the element-wise kernel takes packed rows
+  const int rc = mca_gemm_nt(A, lda, W1, ldb, h, ldh, 1, nullptr, nullptr, 0, 0, M, 2 * ip, K, stream);
+  if (rc != MCA_OK) return rc;
+  return mca_geglu_fwd(h, g, M, (int)ip, stream);
+}
+
+static int check_tn(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* C, int64_t ldc, int64_t N, int64_t K) {
+  if (!A || !B || !C || N <= 0 || K <= 0) return MCA_E_BADARG;
   if (lda % 8 || ldb % 8 || (uintptr_t)A % 16 || (uintptr_t)B % 16) return MCA_E_ALIGN;
   if (lda < (N + 7) / 8 * 8 || ldb < (K + 7) / 8 * 8 || ldc < K) return MCA_E_BADARG;
+  return MCA_OK;
+}
+
+extern "C" int mca_gemm_tn_acc(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, float* C, int64_t ldc,
+                               int64_t R, int64_t N, int64_t K, mca_stream_t stream) {
+  if (R <= 0) return MCA_E_BADARG;
+  const int rc = check_tn(A, lda, B, ldb, C, ldc, N, K);
+  if (rc != MCA_OK) return rc;
   if (R > (1LL << 30)) return MCA_E_UNSUPPORTED;
-  const bool big = N >= 512 && R >= 4096 && g_knob[5] != 1;          // knob 5 = 1 forces the 128x128 kernel, 2 the 256x128 one
-  // 256x256 tiles when the output has at least 8 of them (a 512x512 gradient has 4: the 256x128 kernel with half the
-  // splits, i.e. half the atomic bytes, measured 70 vs 93 us)
-  const bool huge = big && K >= 512 && g_knob[5] != 2 && ((N + 255) / 256) * ((K + 255) / 256) >= 8;
-  const int tiles_k = (int)(huge ? (K + 255) / 256 : (K + 127) / 128);
-  const int tiles_n = big ? (int)((N + 255) / 256) : (int)((N + 127) / 128);
-  const int tiles = tiles_n * tiles_k;
-  // split the reduction: one (big: 1 WG/CU) or two (2 WGs/CU) full rounds of workgroups; every split adds N*K*4 bytes
-  // of fp32 atomics; at least 4 steps of 64 rows each
-  int64_t splits = big ? (tiles <= 16 ? 256 / tiles : 512 / tiles) : (tiles <= 32 ? 512 / tiles : 1024 / tiles);
-  if (huge) splits = 256 / tiles > 0 ? 256 / tiles : 1;
-  if (g_knob[3] > 0) splits = g_knob[3];
-  const int64_t max_splits = (R + 4 * BR - 1) / (4 * BR);
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  if (splits > 65535) splits = 65535;
-  int64_t rps = (R + splits - 1) / splits;
-  rps = (rps + BR - 1) / BR * BR;
-  splits = (R + rps - 1) / rps;
-  if (huge) {
-    static bool attr_dev[64] = {false}; bool& attr = *mca_dev_flag(attr_dev);
-    if (!attr) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_256x256_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              TN2_LDS_BYTES) != hipSuccess)
-        return MCA_E_LAUNCH;
-      attr = true;
-    }
-    hipLaunchKernelGGL(gemm_tn_256x256_kernel, dim3(tiles, (unsigned)splits), dim3(512), TN2_LDS_BYTES, as_stream(stream), A, lda, B,
-                       ldb, C, ldc, (int)R, (int)N, (int)K, tiles_k, (int)rps, g_knob[9]);
-    return launch_status();
-  }
-  if (big) {
-    static bool attr_dev[64] = {false}; bool& attr = *mca_dev_flag(attr_dev);
-    if (!attr) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_256_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              TN256_LDS_BYTES) != hipSuccess)
-        return MCA_E_LAUNCH;
-      attr = true;
-    }
-    hipLaunchKernelGGL(gemm_tn_256_kernel, dim3(tiles, (unsigned)splits), dim3(512), TN256_LDS_BYTES, as_stream(stream), A, lda, B,
-                       ldb, C, ldc, (int)R, (int)N, (int)K, tiles_k, (int)rps, g_knob[9]);
-    return launch_status();
-  }
-  hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles, (unsigned)splits), dim3(256), 0, as_stream(stream), A, lda, B, ldb, C,
-                     ldc, (int)R, (int)N, (int)K, tiles_k, (int)rps, g_knob[2]);
-  return launch_status();
+  const gemm_operands o = {A, lda, B, ldb, C, ldc, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, (int)R, (int)K, nullptr};
+  return launch(mca_plan_gemm_tn(R, N, K, mca_knobs), o, stream);
 }
 
 extern "C" int mca_gemm_tn_acc_group(const mca_tn_desc* d, int n, int64_t R, mca_stream_t stream) {
   if (!d || n <= 0 || n > MCA_TN_MAX_GROUP || R <= 0) return MCA_E_BADARG;
   if (R > (1LL << 30)) return MCA_E_UNSUPPORTED;
-  // The grouped kernel is the 256x256-tile one: members it does not suit (or a group too small to fill the chip) go
-  // through the single-problem entry point, one launch each.
   tn_group g;
   int tiles = 0;
-  bool ok = g_knob[11] != 1 && R >= 4096;          // knob 11 = 1: always one launch per member (A/B)
-  for (int i = 0; i < n && ok; i++) {
-    if (!d[i].A || !d[i].B || !d[i].C || d[i].N <= 0 || d[i].K <= 0) return MCA_E_BADARG;
-    if (d[i].lda % 8 || d[i].ldb % 8 || (uintptr_t)d[i].A % 16 || (uintptr_t)d[i].B % 16) return MCA_E_ALIGN;
-    if (d[i].lda < (d[i].N + 7) / 8 * 8 || d[i].ldb < (d[i].K + 7) / 8 * 8 || d[i].ldc < d[i].K) return MCA_E_BADARG;
-    if (d[i].N < 256 || d[i].K < 256 || d[i].N > (1 << 24) || d[i].K > (1 << 24)) { ok = false; break; }
+  bool all_taken = true;
+  for (int i = 0; i < n; i++) {
+    const int rc = check_tn(d[i].A, d[i].lda, d[i].B, d[i].ldb, d[i].C, d[i].ldc, d[i].N, d[i].K);
+    if (rc != MCA_OK) return rc;
+    const int t = mca_tn_group_member_tiles(d[i].N, d[i].K);
+    all_taken = all_taken && t > 0;
     g.A[i] = d[i].A; g.B[i] = d[i].B; g.C[i] = d[i].C;
     g.lda[i] = d[i].lda; g.ldb[i] = d[i].ldb; g.ldc[i] = d[i].ldc;
     g.N[i] = (int)d[i].N; g.K[i] = (int)d[i].K;
     g.tiles_k[i] = (int)((d[i].K + 255) / 256);
     g.first_tile[i] = tiles;
-    tiles += (int)((d[i].N + 255) / 256) * g.tiles_k[i];
+    tiles += t;
   }
-  if (!ok || n == 1 || tiles < 16 || tiles > 65535) {
+  const mca_tn_group_plan p = mca_plan_gemm_tn_group(all_taken ? tiles : 0, n, R, mca_knobs, num_cus());
+  if (p.grouped < 0) return p.grouped;
+  if (!p.grouped) {          // members the grouped kernel does not suit, or a group too small to fill the chip: one launch each
     for (int i = 0; i < n; i++) {
       const int rc = mca_gemm_tn_acc(d[i].A, d[i].lda, d[i].B, d[i].ldb, d[i].C, d[i].ldc, R, d[i].N, d[i].K, stream);
       if (rc != MCA_OK) return rc;
@@ -1812,69 +1694,43 @@ extern "C" int mca_gemm_tn_acc_group(const mca_tn_desc* d, int n, int64_t R, mca
     return MCA_OK;
   }
   for (int i = n; i <= MCA_TN_MAX_GROUP; i++) g.first_tile[i] = tiles;
-  g.n = n; g.R = (int)R; g.tiles = tiles;
-  // One full round of workgroups (1 per CU).  n_full whole splits of `unit` rows per tile + `spans` workgroups on the tile-major
-  // line of the rows left over (struct tn_group).  A span workgroup pays two pipeline fills and two atomic epilogues, so it gets
-  // `relief` rows less than a cell: unit = (tiles * R + spans * relief) / CUs.  At least 4 steps of 32 rows per workgroup.
-  // knob 3 = s: s uniform splits and no line (the round-3 partition, A/B); knob 6 = r + 1: relief of 32 r rows, -(r + 1): the same without owner segments
-  const int cus = num_cus();
-  const int k6 = g_knob[6];
-  // (a FIXED relief: scaling it down with R - at most an eighth of a cell - was measured and is worse at small R: b = 2, 52 / 60 tiles
-  //  73.6 / 78.0 us with 1,536 rows against 76.9 / 95.0 with 512; b = 16 within 2 % either way.  tools/bench_tn_group.py 2 8 16)
-  const int64_t relief = k6 != 0 ? 32 * (int64_t)((k6 < 0 ? -k6 : k6) - 1) : TN_SPAN_RELIEF;
-  int64_t n_full = cus / tiles, unit, rest, span = 0, spans = 0, own = 0;
-  if (g_knob[3] > 0) {
-    unit = ((R + g_knob[3] - 1) / g_knob[3] + BR2 - 1) / BR2 * BR2;
-    n_full = (R + unit - 1) / unit; rest = 0;                 // uniform splits: the last one is short
-  } else {
-    const int64_t sp0 = cus - n_full * tiles, left = tiles - sp0;          // line workgroups; tiles without an owner among them
-    const bool owners = k6 >= 0 && n_full > 0 && sp0 > 0 && left > 0 && left <= sp0;
-    if (owners) {
-      // a line workgroup reduces rest + left * rest / sp0 rows, a cell `unit` = that + relief:  rest * f + relief = unit,
-      // rest = R - n_full * unit,  f = 1 + left / sp0
-      const double f = 1.0 + (double)left / (double)sp0;
-      unit = (int64_t)(((double)R * f + (double)relief) / ((double)n_full * f + 1.0));
-      if (unit < 4 * BR2) unit = 4 * BR2;
-      unit = (unit + BR2 - 1) / BR2 * BR2;
-      rest = R - n_full * unit;
-    }
-    if (owners && rest >= BR2) {
-      own = sp0;
-      span = (left * rest + sp0 - 1) / sp0;
-      if (span < 4 * BR2) span = 4 * BR2;
-      span = (span + BR2 - 1) / BR2 * BR2;
-      spans = sp0;
-    } else {
-      for (;;) {
-        const int64_t sp = cus - n_full * tiles;                // workgroups left for the line
-        unit = ((int64_t)tiles * R + sp * relief + cus - 1) / cus;
-        if (unit < 4 * BR2) unit = 4 * BR2;
-        unit = (unit + BR2 - 1) / BR2 * BR2;
-        rest = R - n_full * unit;
-        if (rest >= 0 || n_full == 0) break;
-        n_full--;                                               // (tiny R: fewer whole splits)
-      }
-      if (n_full == 0) { rest = R; }
-      if (rest > 0) {
-        const int64_t sp = cus - n_full * tiles > 0 ? cus - n_full * tiles : cus;
-        span = ((int64_t)tiles * rest + sp - 1) / sp;
-        if (span < 4 * BR2) span = 4 * BR2;
-        span = (span + BR2 - 1) / BR2 * BR2;
-        spans = ((int64_t)tiles * rest + span - 1) / span;
-      }
-    }
+  g.n = n; g.R = p.part.R; g.tiles = p.part.tiles;
+  g.unit = p.part.unit; g.n_full = p.part.n_full; g.span = p.part.span; g.own = p.part.own;
+  gemm_operands o = {};
+  o.group = &g;
+  return launch(p.launch, o, stream);
+}
+
+// ---- the plans themselves, for tests and tools (include/mca_hip_debug.h): the planners the entry points above call, with
+// the current knob table; cus = 0 asks the runtime.  Nothing is launched and no device is touched.
+extern "C" int mca_dbg_plan_gemm_nt(int entry, const mca_nt_problem* pr, int cus, mca_gemm_plan* out) {
+  if (!pr || !out) return MCA_E_BADARG;
+  if (cus <= 0) cus = num_cus();
+  switch (entry) {
+    case 0: *out = mca_plan_gemm_nt(*pr, mca_knobs, cus); return MCA_OK;
+    case 1:
+      if (!mca_nt_lnres_supported(pr->M, pr->N, pr->K)) return MCA_E_UNSUPPORTED;
+      *out = mca_plan_gemm_nt_lnres(pr->M, pr->N); return MCA_OK;
+    case 2: *out = mca_plan_gemm_nt_geglu_fwd(pr->M, pr->N, pr->K, mca_knobs, cus); return MCA_OK;
+    case 3: *out = mca_plan_gemm_nt_geglu_bwd(pr->M, pr->N, pr->K, mca_knobs, cus); return MCA_OK;
   }
-  const int64_t grid = n_full * tiles + spans;
-  if (grid <= 0 || grid > (1 << 30)) return MCA_E_UNSUPPORTED;
-  g.span = (int)span; g.own = (int)own;
-  g.unit = (int)unit; g.n_full = (int)n_full;
-  static bool attr_dev[64] = {false}; bool& attr = *mca_dev_flag(attr_dev);
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_256x256_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            TN2_LDS_BYTES) != hipSuccess)
-      return MCA_E_LAUNCH;
-    attr = true;
+  return MCA_E_BADARG;
+}
+extern "C" const char* mca_dbg_gemm_kernel_name(int kernel) { return mca_gemm_kernel_name(kernel); }
+extern "C" int mca_dbg_plan_gemm_tn(int64_t R, int64_t N, int64_t K, mca_gemm_plan* out) {
+  if (!out || R <= 0 || N <= 0 || K <= 0) return MCA_E_BADARG;
+  *out = mca_plan_gemm_tn(R, N, K, mca_knobs);
+  return MCA_OK;
+}
+extern "C" int mca_dbg_plan_gemm_tn_group(const int64_t* N, const int64_t* K, int n, int64_t R, int cus, mca_tn_group_plan* out) {
+  if (!N || !K || !out || n <= 0 || n > MCA_TN_MAX_GROUP || R <= 0) return MCA_E_BADARG;
+  int tiles = 0;
+  bool all_taken = true;
+  for (int i = 0; i < n; i++) {
+    const int t = mca_tn_group_member_tiles(N[i], K[i]);
+    all_taken = all_taken && t > 0;
+    tiles += t;
   }
-  hipLaunchKernelGGL(gemm_tn_256x256_group_kernel, dim3((unsigned)grid), dim3(512), TN2_LDS_BYTES, as_stream(stream), g, g_knob[9]);
-  return launch_status();
+  *out = mca_plan_gemm_tn_group(all_taken ? tiles : 0, n, R, mca_knobs, cus > 0 ? cus : num_cus());
+  return MCA_OK;
 }

@@ -116,6 +116,27 @@ class AttnBwd1Args(C.Structure):
     ]
 
 
+# the GEMM planners' structs (csrc/gemm_plan.h; filled by the mca_dbg_plan_gemm_* hooks)
+class GemmPlan(C.Structure):
+    _fields_ = [(f, C.c_int) for f in ("kernel", "grid_x", "grid_y", "block", "lds_bytes", "n", "tiles_n", "nwg", "tiles_k",
+                                       "rows_per_split", "dbg")]
+
+
+class NtProblem(C.Structure):
+    _fields_ = [("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64), ("out_bf16", C.c_int), ("res_period", C.c_int64),
+                ("C", C.c_uint64), ("bias", C.c_uint64), ("residual", C.c_uint64), ("ldc", C.c_int64), ("ldres", C.c_int64)]
+
+
+class TnPartition(C.Structure):
+    _fields_ = [(f, C.c_int) for f in ("tiles", "R", "unit", "n_full", "span", "own")]
+
+
+class TnGroupPlan(C.Structure):
+    _fields_ = [("grouped", C.c_int), ("launch", GemmPlan), ("part", TnPartition)]
+
+
+PLAN_NT, PLAN_LNRES, PLAN_GEGLU_FWD, PLAN_GEGLU_BWD = range(4)          # `entry` of mca_dbg_plan_gemm_nt
+
 _P, _I64, _I, _F = C.c_void_p, C.c_int64, C.c_int, C.c_float
 
 # name -> (restype, argtypes).  Must list EVERY symbol include/mca_hip.h declares (tests check this).
@@ -180,6 +201,10 @@ SIGNATURES = {
 DEBUG_SIGNATURES = {
     "mca_debug_set": (_I, [_I, _I]),
     "mca_debug_reset": (_I, []),
+    "mca_dbg_gemm_kernel_name": (C.c_char_p, [_I]),
+    "mca_dbg_plan_gemm_nt": (_I, [_I, C.POINTER(NtProblem), _I, C.POINTER(GemmPlan)]),
+    "mca_dbg_plan_gemm_tn": (_I, [_I64, _I64, _I64, C.POINTER(GemmPlan)]),
+    "mca_dbg_plan_gemm_tn_group": (_I, [C.POINTER(_I64), C.POINTER(_I64), _I, _I64, _I, C.POINTER(TnGroupPlan)]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import gemm_shapes as GS          # the GEMM shape lists: tests/test_gemm_plan_cpu.py asserts which kernels they reach
 
 
 pytestmark = pytest.mark.gpu
@@ -32,9 +33,7 @@ def bf(x):
 
 
 # ------------------------------------------------------------------------------------------------ GEMM
-@pytest.mark.parametrize("M,N,K", [(300, 200, 128), (1000, 1536, 512), (129, 2816, 512), (16, 512, 512), (4060, 512, 1408),
-                                   (4100, 1536, 320), (2600, 2816, 512),          # persistent kernels, grouped column tiles
-                                   (17920, 1024, 192), (17700, 1024, 256)])       # 280 tiles of 256 x 256 on 256 CUs: second tile per workgroup, shortest k-loops
+@pytest.mark.parametrize("M,N,K", GS.NT)
 def test_gemm_nt(H, M, N, K):
     g = torch.Generator(device="cuda").manual_seed(1)
     A = bf(torch.randn(M, K, device="cuda", generator=g))
@@ -50,15 +49,24 @@ def test_gemm_nt(H, M, N, K):
     Cb = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
     H.call("mca_gemm_nt", A.data_ptr(), K, B.data_ptr(), K, Cb.data_ptr(), N, 1, None, None, 0, 0, M, N, K, H.stream_ptr())
     assert rel(Cb.float(), ref) < 4e-3
+    # the remaining epilogue forms (their own kernel instantiations): bias alone, bf16 with bias and residual
+    H.call("mca_gemm_nt", A.data_ptr(), K, B.data_ptr(), K, C32.data_ptr(), N, 0, bias.data_ptr(), None, 0, 0, M, N, K, H.stream_ptr())
+    assert rel(C32, ref + bias) < 1e-5
+    H.call("mca_gemm_nt", A.data_ptr(), K, B.data_ptr(), K, Cb.data_ptr(), N, 1, bias.data_ptr(), None, 0, 0, M, N, K, H.stream_ptr())
+    assert rel(Cb.float(), ref + bias) < 4e-3
+    H.call("mca_gemm_nt", A.data_ptr(), K, B.data_ptr(), K, Cb.data_ptr(), N, 1, bias.data_ptr(), res.data_ptr(), N, 0, M, N, K, H.stream_ptr())
+    assert rel(Cb.float(), ref + bias + res) < 4e-3
     # broadcast residual (row % period)
     per = 16 if M % 16 == 0 else 0
     if per:
         r2 = torch.randn(per, N, device="cuda", generator=g)
         H.call("mca_gemm_nt", A.data_ptr(), K, B.data_ptr(), K, C32.data_ptr(), N, 0, None, r2.data_ptr(), N, per, M, N, K, H.stream_ptr())
         assert rel(C32, ref + r2.repeat(M // per, 1)) < 1e-5
+        H.call("mca_gemm_nt", A.data_ptr(), K, B.data_ptr(), K, Cb.data_ptr(), N, 1, None, r2.data_ptr(), N, per, M, N, K, H.stream_ptr())
+        assert rel(Cb.float(), ref + r2.repeat(M // per, 1)) < 4e-3
 
 
-@pytest.mark.parametrize("M,N,K", [(2304, 512, 512), (4100, 512, 1408), (2100, 256, 576)])
+@pytest.mark.parametrize("M,N,K", GS.NT_LNRES)
 def test_gemm_nt_lnres(H, M, N, K):
     """C = A B^T + LayerNorm(x), the LayerNorm recomputed in the epilogue from x and the statistics the LN kernel saved."""
     g = torch.Generator(device="cuda").manual_seed(11)
@@ -80,8 +88,7 @@ def test_gemm_nt_lnres(H, M, N, K):
                                      gamma.data_ptr(), 100, N, K, H.stream_ptr()) == -3
 
 
-@pytest.mark.parametrize("R,N,K,lda,ldb", [(1000, 512, 512, 512, 512), (777, 1365, 512, 2816, 512), (2048, 512, 1365, 512, 1408),
-                                           (16, 512, 512, 512, 512), (500, 128, 74, 128, 128), (5000, 1024, 512, 1536, 512)])
+@pytest.mark.parametrize("R,N,K,lda,ldb", GS.TN_ACC)
 def test_gemm_tn_acc(H, R, N, K, lda, ldb):
     g = torch.Generator(device="cuda").manual_seed(2)
     A = bf(torch.randn(R, lda, device="cuda", generator=g))
@@ -92,17 +99,7 @@ def test_gemm_tn_acc(H, R, N, K, lda, ldb):
     assert rel(Cg, ref) < 2e-5
 
 
-@pytest.mark.parametrize("R,members", [
-    (8192, [(1536, 512, 1536, 512), (1365, 512, 2816, 512), (1365, 512, 2816, 512), (512, 1365, 512, 1408)]),   # a layer's four
-    # a layer's five (with the out-projection): 52 tiles = 4 whole splits + 48 spans that end one tile's rows and begin the next's
-    (8200, [(1536, 512, 1536, 512), (1365, 512, 2816, 512), (1365, 512, 2816, 512), (512, 1365, 512, 1408), (512, 512, 512, 512)]),
-    # ... and the pooling key/value projection on top (the top layer's launch), at the b = 8 row count
-    (20304, [(1536, 512, 1536, 512), (1365, 512, 2816, 512), (1365, 512, 2816, 512), (512, 1365, 512, 1408), (512, 512, 512, 512),
-             (1024, 512, 1024, 512)]),
-    (4100, [(512, 512, 512, 512), (300, 700, 304, 704), (1024, 256, 1024, 256), (256, 256, 256, 256), (515, 260, 520, 264)]),
-    (5000, [(512, 512, 512, 512), (100, 512, 104, 512)]),          # a member the grouped kernel does not take -> single launches
-    (300, [(512, 512, 512, 512), (512, 256, 512, 256)]),           # too few rows -> single launches
-])
+@pytest.mark.parametrize("R,members", GS.TN_GROUP)
 def test_gemm_tn_acc_group(H, R, members):
     """mca_gemm_tn_acc_group == the single-problem results, member by member (incl. column offsets into a shared operand)"""
     g = torch.Generator(device="cuda").manual_seed(12)
@@ -120,7 +117,7 @@ def test_gemm_tn_acc_group(H, R, members):
     for (A, B, Cg), ref in zip(keep, refs):
         assert rel(Cg, ref) < 2e-5
     # uniform row splits (knob 3: the partition without the tile-major line) add the same products once more
-    H.lib().mca_debug_set(3, 3)
+    H.lib().mca_debug_set(3, GS.TN_GROUP_UNIFORM_SPLITS)
     try:
         H.call("mca_gemm_tn_acc_group", C.byref(arr), len(members), R, H.stream_ptr())
         torch.cuda.synchronize()
@@ -270,8 +267,7 @@ def test_geglu(H):
     assert rel(dh.float(), hr.grad) < 4e-3
 
 
-@pytest.mark.parametrize("rows,ip,D", [(500, 384, 128), (4100, 384, 128), (4100, 384, 512), (2304, 448, 320), (2100, 1408, 512),
-                                       (8200, 1408, 192), (8200, 1408, 512)])          # 363 tiles: a second tile per workgroup
+@pytest.mark.parametrize("rows,ip,D", GS.GEGLU_FWD)
 def test_gemm_geglu_fwd_fused(H, rows, ip, D):
     """h = x @ W1^T (both halves, bf16) and g = a * gelu(gate) in one pass; the large-K cases run the persistent kernel
     (tile columns = 64 "a" + 64 "gate" rows of W1), 4100 rows end in a partial 256-row tile."""
@@ -287,8 +283,7 @@ def test_gemm_geglu_fwd_fused(H, rows, ip, D):
     assert rel(out.float(), torch.nn.functional.gelu(hb[:, ip:]) * hb[:, :ip]) < 4e-3
 
 
-@pytest.mark.parametrize("rows,ip,D", [(500, 384, 128), (4100, 384, 128), (4100, 384, 512), (2304, 640, 320), (2100, 1408, 512),
-                                       (41100, 384, 128), (41100, 384, 512)])          # >= 40,960 rows: the 256-row kernels
+@pytest.mark.parametrize("rows,ip,D", GS.GEGLU_BWD)
 def test_gemm_geglu_bwd_fused(H, rows, ip, D):
     g = torch.Generator(device="cuda").manual_seed(41)
     h = bf(torch.randn(rows, 2 * ip, device="cuda", generator=g))
