@@ -224,6 +224,37 @@ typedef struct {
 /* dim_head is fixed at 64; query tile 128 rows, key tile 64.                                     */
 int mca_attn_fwd(const mca_attn_fwd_args* args, mca_stream_t stream);
 
+/* Attention READOUT (model.py:87-103: Attention.forward with return_attn=True returns softmax(q·k^T) after its two
+ * masked_fill; here the (b, h, nq, nk) matrix is never written).  One launch per attention, after mca_attn_fwd on the same
+ * operands (same conventions: head = 64 contiguous bf16, q_bstride 0 for the pooling query, MCA_ATTN_Q_PRESCALED required,
+ * the forward's 128 x 64 tile lists).  lse is the array the forward wrote and is not recomputed: p[i][j] = exp2(q_i·k_j - lse[i]) for a key j the row may see
+ * ((qmask[i] >> keyinfo[b][j]) & 1), exactly 0 for every other key.
+ *   mass[b, h, i, g] (fp32, every element written) = sum of p[i][j] over the keys j with keyinfo[b][j] == g: the share of row
+ *     i's softmax on key group g < n_groups (1 <= n_groups <= 31).  A uniform row (lse = +inf) gets uniform_mass[g], which the
+ *     caller sets to (keys with static group g) / nk: the reference's softmax of a fully masked row is uniform over ALL nk
+ *     keys, padded and blocked ones included.
+ *   probs[b, h, r, j] (fp32, optional: NULL to skip) = p[row0 + r][j] for r < n_rows and every j < nk, every element written
+ *     (keys of tiles the schedule skips included: 0); 1 / nk on a uniform row.  The window need not be aligned.
+ * fp32 sums in a fixed order, no atomics: bitwise repeatable.  row0 / n_rows are read only when probs is given.             */
+typedef struct {
+  const uint16_t* q; int64_t q_bstride; int64_t q_ld;     /* q[b*q_bstride + i*q_ld + h*64 + d]   */
+  const uint16_t* k; int64_t kv_bstride; int64_t kv_ld;
+  const float* lse;                 /* (b, heads, nq) log2-domain, as written by the forward         */
+  const uint32_t* qmask;            /* (nq)                                                          */
+  const uint8_t* keyinfo;           /* (b, nk_pad)                                                   */
+  const uint8_t* ktile_flags;       /* (b, n_ktiles)                                                 */
+  const int32_t* q_ptr; const uint32_t* q_kt; const int32_t* q_order;
+  int batch, heads, nq, nk, nk_pad, n_qtiles, n_ktiles;
+  float scale;                      /* dim_head ** -0.5 (already folded into q)                      */
+  int flags;                        /* MCA_ATTN_Q_PRESCALED                                          */
+  int n_groups;
+  const float* uniform_mass;        /* (n_groups)                                                    */
+  float* mass;                      /* (b, heads, nq, n_groups)                                      */
+  float* probs;                     /* (b, heads, n_rows, nk) or NULL                                */
+  int row0, n_rows;
+} mca_attn_readout_args;
+int mca_attn_readout(const mca_attn_readout_args* args, mca_stream_t stream);
+
 /* ---- EAO baseline (model.py:481-596): every modality alone and every combination of modalities is one SEGMENT of a
  * super-sequence; the attention kernels' key groups make the attention block-diagonal over segments.
  * dst[b, r, :] (+)= src[b, r, :], r < rows: replicates a modality's encoded token block into its segments (accumulate = 0)

@@ -3,7 +3,10 @@ YAML), run the model in eval mode over the train and test splits, and write
 ``<output_dir>/{train,eval}_{embeddings,masks,labels}.pt`` in the reference's format (dict name -> (n, D) tensor;
 dict modality -> (n,) bool; (n, ...) labels) — the files ``lp_accel_gpu.py`` of the reference consumes.
 
-    python infer_accel_gpu.py <config.yaml> [--synthetic BATCHES]
+    python infer_accel_gpu.py <config.yaml> [--synthetic BATCHES] [--readout]
+
+--readout: also write ``{train,eval}_attention.pt``: ``{"groups": [...], "slot_mass": {slot: (n, G)}}``, for every sample and
+output slot the share of the slot's pooling attention (head mean) that fell on each key group (``MCA.attention_readout``).
 """
 import importlib
 import os
@@ -21,6 +24,7 @@ def main():
     if len(sys.argv) < 2:
         raise SystemExit(__doc__)
     synthetic = int(sys.argv[sys.argv.index("--synthetic") + 1]) if "--synthetic" in sys.argv else 0
+    readout = "--readout" in sys.argv
     assert torch.cuda.device_count() >= 1
     device = torch.device("cuda", 0)
     config = P.config.training_config(sys.argv[1])
@@ -53,6 +57,7 @@ def main():
     with torch.no_grad():
         for tv, dl in splits.items():
             embeddings, masks, labels = defaultdict(list), defaultdict(list), []
+            slot_mass, groups = defaultdict(list), None
             for batch in dl:
                 batch_labels = batch.pop(label_col)
                 batch = {k: {kk: vv.to(device) for kk, vv in v.items()} for k, v in batch.items()}
@@ -65,9 +70,17 @@ def main():
                 for k, v in outputs.items():
                     embeddings[k].append(v.detach().cpu())
                 labels.append(batch_labels["data"].detach().cpu())
+                if readout:          # (a second, no_loss forward of the same batch plus one launch: the files above do not change)
+                    ro = model.attention_readout(batch, layers=[], pool=True)
+                    groups = ro["groups"]
+                    for k, v in ro["slot_mass"].items():
+                        slot_mass[k].append(v.detach().cpu())
             torch.save({k: torch.cat(v, 0) for k, v in masks.items()}, f"{config.output_dir}/{tv}_masks.pt")
             torch.save({k: torch.cat(v, 0) for k, v in embeddings.items()}, f"{config.output_dir}/{tv}_embeddings.pt")
             torch.save(torch.cat(labels, 0), f"{config.output_dir}/{tv}_labels.pt")
+            if readout:
+                torch.save({"groups": groups, "slot_mass": {k: torch.cat(v, 0) for k, v in slot_mass.items()}},
+                           f"{config.output_dir}/{tv}_attention.pt")
             print(f"{tv}: {sum(x.shape[0] for x in labels)} samples -> {config.output_dir}/{tv}_*.pt", flush=True)
 
 

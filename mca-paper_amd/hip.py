@@ -67,6 +67,19 @@ class AttnFwdArgs(C.Structure):
     ]
 
 
+class AttnReadoutArgs(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("q_bstride", C.c_int64), ("q_ld", C.c_int64),
+        ("k", C.c_void_p), ("kv_bstride", C.c_int64), ("kv_ld", C.c_int64),
+        ("lse", C.c_void_p), ("qmask", C.c_void_p), ("keyinfo", C.c_void_p), ("ktile_flags", C.c_void_p),
+        ("q_ptr", C.c_void_p), ("q_kt", C.c_void_p), ("q_order", C.c_void_p),
+        ("batch", C.c_int), ("heads", C.c_int), ("nq", C.c_int), ("nk", C.c_int), ("nk_pad", C.c_int),
+        ("n_qtiles", C.c_int), ("n_ktiles", C.c_int), ("scale", C.c_float), ("flags", C.c_int),
+        ("n_groups", C.c_int), ("uniform_mass", C.c_void_p), ("mass", C.c_void_p), ("probs", C.c_void_p),
+        ("row0", C.c_int), ("n_rows", C.c_int),
+    ]
+
+
 ATTN_Q_PRESCALED = 1
 ATTN_LAZY_REFERENCE = 2          # mca_attn_fwd: lazy softmax reference (include/mca_hip.h)
 
@@ -170,6 +183,7 @@ SIGNATURES = {
     "mca_attn_vmean": (_I, [_P, _I64, _I64, _P, _I, _I, _I, _P]),
     "mca_attn_vmean_if_needed": (_I, [_P, _I64, _I64, _P, _I, _I, _I, _P, _I, _P]),
     "mca_attn_fwd": (_I, [C.POINTER(AttnFwdArgs), _P]),
+    "mca_attn_readout": (_I, [C.POINTER(AttnReadoutArgs), _P]),
     "mca_attn_quant_mxfp8": (_I, [_P, _I64, _I64, _P, _P, _I64, _I64, C.POINTER(AttnFp8Operands), _I, _I, _I, _P]),
     "mca_attn_fwd_fp8": (_I, [C.POINTER(AttnFwdArgs), C.POINTER(AttnFp8Operands), _P]),
     "mca_attn_bwd_prep": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _I, _I, _I, _I, _P]),

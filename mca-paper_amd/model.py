@@ -162,6 +162,20 @@ class MCA(nn.Module):
         """Same contract as the reference's ``MCA.forward`` (model.py:448-478)."""
         return self.engine.model_forward(batch, no_loss=no_loss)
 
+    # ---- where the attention looked (the reference's Attention.forward(return_attn=True), model.py:87-103) ----------
+    def attention_readout(self, batch, layers=None, pool=True, probs_rows=None):
+        """Per-group attention mass of a no-grad ``no_loss`` forward, from the q / k / log-sum-exp the forward saved
+        (readout.py; one extra launch per requested attention, the (b, h, N, N) matrix is never written).
+
+        layers: fusion layers to read (None = all); pool: the attentive pooling as well;
+        probs_rows: {"pool": (row0, n)} and / or {layer: (row0, n)}: also return the probabilities of those query rows.
+        -> {"groups": readout.group_names(self), "layer_mass": {i: (b, H, N, G)}, "pool_mass": (b, H, R, G),
+            "slot_mass": {slot of output_slots(): (b, G), the head mean of the slot's pooling row},
+            "modality_sample_mask": as the forward's, "probs": {key: (b, H, n, N)} when probs_rows is given}.
+        A fully masked row reads as the reference's uniform softmax: a group's share is its key count over N."""
+        from . import readout
+        return readout.attention_readout(self, batch, layers=layers, pool=pool, probs_rows=probs_rows)
+
     # ---- names of the pooled slots (model.py:181-191) ------------------------------------------------
     def output_slots(self) -> Dict[object, int]:
         M = len(self.modality_types)
