@@ -471,6 +471,55 @@ int mca_probe_tn_f32(const float* a, int64_t lda, const float* b, int64_t ldb, c
 /* acc[0] += (sum of n loss partials, fixed order) / count */
 int mca_probe_loss_accum(const float* loss_part, int64_t n, int64_t count, float* acc, mca_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Deterministic mode: fixed-order forms of the five entry points whose parameter gradients are sums of
+ * fp32 atomics ("Deterministic mode").  Each takes the arguments of its plain form plus
+ * `scratch` (device, fp32) and its size in floats; the *_scratch queries (host only, nothing launched)
+ * give the floats a problem needs.  A scratch that is NULL or too small: MCA_E_BADARG, nothing launched.
+ * Every contributing workgroup STORES its partial into slot s of the scratch (s = its row split / slab
+ * index, a function of the problem shape, the knob table and - grouped form only - the CU count; never
+ * of timing or placement); a second launch on the same stream then computes, per destination element,
+ *     dst = dst + (((p_0 + p_1) + p_2) + ... + p_{S-1})        sequentially in fp32,
+ * with a plain read-modify-write: the caller orders calls that target the same tensor (stream order
+ * does).  The scratch needs no zeroing and holds nothing between calls; calls on one stream may share it.
+ * The partials are the plain forms' own (same tiles, same row ranges, same per-row arithmetic).
+ *
+ * Slot layouts (slot s at scratch + s * slot_stride, all packed fp32):
+ *   mca_gemm_tn_acc_det        S = the plain form's row splits; slot = [N][K], slot_stride = N*K.
+ *                              S == 1: the plain kernel runs, need 0, scratch unused.
+ *   mca_gemm_tn_acc_group_det  grouped launch: S uniform row splits of every tile (S = CUs / tiles, at
+ *                              least 128 rows each); slot = member 0's [N_0][K_0], then member 1's, ...;
+ *                              slot_stride = sum N_i*K_i.  S == 1: need 0.  Groups the grouped kernel does
+ *                              not take: one mca_gemm_tn_acc_det per member in order, each with its own
+ *                              layout from scratch + 0; need = the largest member's.
+ *   mca_layernorm_bwd_det      S = workgroups of the kernel form the call takes; slot = [3][cols]: dgamma,
+ *                              dbeta, dxsum partials (rows of a NULL target are not written), slot_stride
+ *                              = 3*cols.  The need is 3*cols * the largest S over the three kernel forms
+ *                              for (rows, cols), so it does not depend on which pointers are NULL.
+ *   mca_reduce_rows_det        S = row slabs; slot = [period][cols], slot_stride = period*cols.
+ *   mca_tab_value_bwd_det      S = row slabs; slot = [2][cols]: dw1, db1; slot_stride = 2*cols.
+ * (S and the partition for a weight gradient: mca_dbg_plan_gemm_tn_det / _group_det, mca_hip_debug.h.)
+ * cus: CU count to plan the grouped form for, 0 = the current device's.
+ * --------------------------------------------------------------------------------------------- */
+int64_t mca_gemm_tn_acc_det_scratch(int64_t R, int64_t N, int64_t K);
+int mca_gemm_tn_acc_det(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, float* C, int64_t ldc,
+                        int64_t R, int64_t N, int64_t K, float* scratch, int64_t scratch_floats, mca_stream_t stream);
+int64_t mca_gemm_tn_acc_group_det_scratch(const int64_t* N, const int64_t* K, int n, int64_t R, int cus);
+int mca_gemm_tn_acc_group_det(const mca_tn_desc* d, int n, int64_t R, float* scratch, int64_t scratch_floats, mca_stream_t stream);
+int64_t mca_layernorm_bwd_det_scratch(int64_t rows, int cols);
+int mca_layernorm_bwd_det(const float* dy, int64_t ldy, int64_t y_bstride, int64_t period,
+                          const float* x, int64_t ldx, const float* gamma,
+                          const float* mean, const float* rstd, const uint8_t* rowmask,
+                          float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16,
+                          float* dgamma, float* dbeta, float* dxsum, int64_t rows, int cols,
+                          float* scratch, int64_t scratch_floats, mca_stream_t stream);
+int64_t mca_reduce_rows_det_scratch(int64_t rows, int64_t period, int cols);
+int mca_reduce_rows_det(const float* src, int64_t lds, int64_t src_bstride, int64_t period, float* dst, int64_t ldd,
+                        int64_t rows, int cols, float* scratch, int64_t scratch_floats, mca_stream_t stream);
+int64_t mca_tab_value_bwd_det_scratch(int64_t rows, int cols);
+int mca_tab_value_bwd_det(const float* dh1, int64_t ld, const uint16_t* h1, const float* x, float* dw1, float* db1,
+                          int64_t rows, int cols, float max_value, float* scratch, int64_t scratch_floats, mca_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

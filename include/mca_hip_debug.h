@@ -46,6 +46,12 @@ int mca_dbg_plan_gemm_nt(int entry, const struct mca_nt_problem* problem, int cu
 int mca_dbg_plan_gemm_tn(int64_t R, int64_t N, int64_t K, struct mca_gemm_plan* out);
 int mca_dbg_plan_gemm_tn_group(const int64_t* N, const int64_t* K, int n, int64_t R, int cus, struct mca_tn_group_plan* out);
 const char* mca_dbg_gemm_kernel_name(int kernel);
+/* The plans of the deterministic weight-gradient forms (mca_gemm_tn_acc_det, mca_gemm_tn_acc_group_det; structs in csrc/gemm_plan.h):
+ * the launch, the slot count, the slot stride and the scratch floats, with the current knob table. */
+struct mca_tn_det_plan;
+struct mca_tn_group_det_plan;
+int mca_dbg_plan_gemm_tn_det(int64_t R, int64_t N, int64_t K, struct mca_tn_det_plan* out);
+int mca_dbg_plan_gemm_tn_group_det(const int64_t* N, const int64_t* K, int n, int64_t R, int cus, struct mca_tn_group_det_plan* out);
 #ifdef __cplusplus
 }
 #endif

@@ -111,3 +111,7 @@ static inline bool mca_dyn_lds(int bytes) {
 
 static inline hipStream_t as_stream(mca_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int launch_status() { return hipGetLastError() == hipSuccess ? MCA_OK : MCA_E_LAUNCH; }
+
+// The reduce launch of every deterministic form (defined in elementwise.hip): dst[r * ldd + c] = dst[r * ldd + c] +
+// (((p_0 + p_1) + p_2) + ...), p_s = scratch[s * slot_stride + r * cols + c], for r < rows, c < cols.  Not part of the C ABI.
+int mca_det_reduce(const float* scratch, int64_t slot_stride, int slots, float* dst, int64_t ldd, int64_t rows, int cols, mca_stream_t stream);

@@ -235,7 +235,11 @@ extern "C" int mca_layernorm_fwd(const float* x, int64_t ldx, const float* gamma
 // dgamma += sum_rows dy*xhat;  dbeta += sum_rows dy.   Per-block partials in registers, one atomic
 // per column per block.
 // =====================================================================================================
-template <int VEC>
+// DET (the three backward kernels, reduce_rows_kernel, tab_value_bwd_kernel): the deterministic forms' last lines.  dgamma / dbeta /
+// dxsum (dst, dw1 / db1) then point into the caller's scratch and every workgroup STORES its partial, zero or not, into the slot
+// of its slab instead of adding it atomically; det_reduce_kernel adds the slots in ascending order.  DET = false is the code it
+// always was.  Slot layouts: include/mca_hip.h.
+template <int VEC, bool DET = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(
     const float* __restrict__ dy, int64_t ldy, int64_t y_bstride, int64_t period,
     const float* __restrict__ x, int64_t ldx, const float* __restrict__ gamma,
@@ -318,7 +322,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(
     __syncthreads();
     for (int c = threadIdx.x; c < cols; c += 256) {
       const float t = red[0][c] + red[1][c] + red[2][c] + red[3][c];
-      if (t != 0.f) atomicAdd(target + c, t);
+      if constexpr (DET) target[(int64_t)blockIdx.x * 3 * cols + c] = t;
+      else if (t != 0.f) atomicAdd(target + c, t);
     }
     __syncthreads();
   }
@@ -326,7 +331,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(
 
 // Trunk form of the backward (gamma only, no mask / period, fp32 dx + bf16 copy, cols % 256 == 0): two rows per wavefront
 // and iteration, as in ln_fwd_trunk_kernel (8 KB of loads in flight per wavefront instead of 4).
-template <int NI>
+template <int NI, bool DET = false>
 __global__ __launch_bounds__(256) void ln_bwd_trunk_kernel(const float* __restrict__ dy, int64_t ldy, const float* __restrict__ x, int64_t ldx,
                                                             const float* __restrict__ gamma, const float* __restrict__ mean_in,
                                                             const float* __restrict__ rstd_in, float* __restrict__ dx, int64_t lddx,
@@ -388,7 +393,8 @@ __global__ __launch_bounds__(256) void ln_bwd_trunk_kernel(const float* __restri
   __syncthreads();
   for (int c = threadIdx.x; c < cols; c += 256) {
     const float t = red[0][c] + red[1][c] + red[2][c] + red[3][c];
-    if (t != 0.f) atomicAdd(dgamma + c, t);
+    if constexpr (DET) dgamma[(int64_t)blockIdx.x * 3 * cols + c] = t;
+    else if (t != 0.f) atomicAdd(dgamma + c, t);
   }
 }
 
@@ -396,7 +402,7 @@ __global__ __launch_bounds__(256) void ln_bwd_trunk_kernel(const float* __restri
 // rows: a thread owns a column and every (256 / CW)-th row of its workgroup's slab (CW = 64 / 128 / 256 columns per
 // workgroup: a 74-column norm keeps 2 x 74 of 256 threads busy instead of 74), coalesced along the columns, no wavefront
 // reductions; the row sub-lanes are added through LDS, then one atomic per column (the row form spent 33 us on 12,000 x 74 values).
-template <int CW>
+template <int CW, bool DET = false>
 __global__ __launch_bounds__(256) void ln_bwd_params_kernel(const float* __restrict__ dy, int64_t ldy, int64_t y_bstride, int64_t period,
                                                              const float* __restrict__ x, int64_t ldx, const float* __restrict__ mean_in,
                                                              const float* __restrict__ rstd_in, const uint8_t* __restrict__ rowmask,
@@ -429,27 +435,63 @@ __global__ __launch_bounds__(256) void ln_bwd_params_kernel(const float* __restr
     for (int k = 0; k < RY; k++) { dg += red[0][k][tx]; db += red[1][k][tx]; }          // fixed order
   }
   if (c >= cols) return;
-  if (dgamma && dg != 0.f) atomicAdd(dgamma + c, dg);
-  if (dbeta && db != 0.f) atomicAdd(dbeta + c, db);
+  if constexpr (DET) {
+    if (dgamma) dgamma[(int64_t)blockIdx.y * 3 * cols + c] = dg;
+    if (dbeta) dbeta[(int64_t)blockIdx.y * 3 * cols + c] = db;
+  } else {
+    if (dgamma && dg != 0.f) atomicAdd(dgamma + c, dg);
+    if (dbeta && db != 0.f) atomicAdd(dbeta + c, db);
+  }
 }
 
-extern "C" int mca_layernorm_bwd(const float* dy, int64_t ldy, int64_t y_bstride, int64_t period,
-                                 const float* x, int64_t ldx, const float* gamma,
-                                 const float* mean, const float* rstd, const uint8_t* rowmask,
-                                 float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16,
-                                 float* dgamma, float* dbeta, float* dxsum, int64_t rows, int cols, mca_stream_t stream) {
-  if (!dy || !x || !gamma || !mean || !rstd || rows < 0 || cols <= 0 || cols > 1024) return MCA_E_BADARG;
-  if (rows == 0) return MCA_OK;
+// The grids of the three forms: one place for the launches and for the deterministic form's scratch need (a slot per workgroup
+// slab).  Knob 14 as described in include/mca_hip_debug.h.
+static inline int64_t ln_bwd_params_slabs(int64_t rows, int cols, int64_t* rpb_out) {
+  const int cw = cols <= 64 ? 64 : (cols <= 128 ? 128 : 256);
+  const int chunks = (cols + cw - 1) / cw;
+  int64_t slabs = 1024 / chunks;          // four rounds of workgroups at most (each ends with one atomic per column)
+  if (slabs > (rows + 31) / 32) slabs = (rows + 31) / 32;
+  if (slabs < 1) slabs = 1;
+  const int64_t rpb = (rows + slabs - 1) / slabs;
+  if (rpb_out) *rpb_out = rpb;
+  return (rows + rpb - 1) / rpb;
+}
+static inline int64_t ln_bwd_trunk_blocks(int64_t rows) {
+  // one workgroup per CU at most: every workgroup ends with one atomic per column on dgamma, and 1024 of them on the same
+  // 512 addresses cost more than the extra loads in flight bring (b = 8: 40.8 -> 28.5 us, b = 32: 108.7 -> 104.0 us;
+  // knob 14 = another cap, tools/bench_ln.py)
+  int64_t nb = (rows + 7) / 8;
+  const int64_t cap = mca_knobs[14] > 0 ? mca_knobs[14] : 256;
+  return nb > cap ? cap : nb;
+}
+static inline int64_t ln_bwd_general_blocks(int64_t rows) {
+  int64_t blocks = (rows + 3) / 4;
+  // every workgroup ends with one atomic per column on the same dgamma / dbeta / dxsum addresses, and a wavefront has one row in
+  // flight: few workgroups at few rows, up to four per CU at many (measured, tools/bench_ln_encoder.py: 3,600 rows 14.5 us at
+  // 256 against 30.7 at 1,024; 48,000 rows 134 us at 256 against 70 at 1,024)
+  int64_t bcap = rows / 32;
+  if (bcap < 256) bcap = 256;
+  if (bcap > 1024) bcap = 1024;
+  if (mca_knobs[14] > 0) bcap = mca_knobs[14];
+  return blocks > bcap ? bcap : blocks;
+}
+
+// DET: dgamma / dbeta / dxsum point at slot 0 of the scratch; *slots = the workgroup slabs that wrote a slot each
+template <bool DET>
+static int ln_bwd_launch(const float* dy, int64_t ldy, int64_t y_bstride, int64_t period,
+                         const float* x, int64_t ldx, const float* gamma,
+                         const float* mean, const float* rstd, const uint8_t* rowmask,
+                         float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16,
+                         float* dgamma, float* dbeta, float* dxsum, int64_t rows, int cols, mca_stream_t stream, int64_t* slots) {
+  *slots = 0;
   if (!dx && !dx_bf16 && !dxsum && mca_knobs[12] != 1) {          // parameter gradients only
     if (!dgamma && !dbeta) return MCA_OK;
     const int cw = cols <= 64 ? 64 : (cols <= 128 ? 128 : 256);
     const int chunks = (cols + cw - 1) / cw;
-    int64_t slabs = 1024 / chunks;          // four rounds of workgroups at most (each ends with one atomic per column)
-    if (slabs > (rows + 31) / 32) slabs = (rows + 31) / 32;
-    if (slabs < 1) slabs = 1;
-    const int64_t rpb = (rows + slabs - 1) / slabs;
-    const dim3 grid(chunks, (unsigned)((rows + rpb - 1) / rpb));
-#define LNP_LAUNCH(CW) hipLaunchKernelGGL(ln_bwd_params_kernel<CW>, grid, dim3(256), 0, as_stream(stream), dy, ldy, y_bstride, period, x, ldx, mean, rstd, \
+    int64_t rpb;
+    const dim3 grid(chunks, (unsigned)ln_bwd_params_slabs(rows, cols, &rpb));
+    *slots = grid.y;
+#define LNP_LAUNCH(CW) hipLaunchKernelGGL((ln_bwd_params_kernel<CW, DET>), grid, dim3(256), 0, as_stream(stream), dy, ldy, y_bstride, period, x, ldx, mean, rstd, \
                                           rowmask, dgamma, dbeta, rows, cols, rpb)
     if (cw == 64) LNP_LAUNCH(64); else if (cw == 128) LNP_LAUNCH(128); else LNP_LAUNCH(256);
 #undef LNP_LAUNCH
@@ -460,33 +502,86 @@ extern "C" int mca_layernorm_bwd(const float* dy, int64_t ldy, int64_t y_bstride
                    ((uintptr_t)x % 16 == 0) && ((uintptr_t)dy % 16 == 0) && (!dx || (uintptr_t)dx % 16 == 0);
   if (vec && !rowmask && period <= 0 && !dbeta && !dxsum && dgamma && (cols == 256 || cols == 512 || cols == 1024) &&
       (uintptr_t)gamma % 16 == 0 && mca_knobs[12] != 1) {          // knob 12 = 1: general kernel (A/B)
-    // one workgroup per CU at most: every workgroup ends with one atomic per column on dgamma, and 1024 of them on the same
-    // 512 addresses cost more than the extra loads in flight bring (b = 8: 40.8 -> 28.5 us, b = 32: 108.7 -> 104.0 us;
-    // knob 14 = another cap, tools/bench_ln.py)
-    int64_t nb = (rows + 7) / 8;
-    const int64_t cap = mca_knobs[14] > 0 ? mca_knobs[14] : 256;
-    if (nb > cap) nb = cap;
-    if (cols == 256) hipLaunchKernelGGL(ln_bwd_trunk_kernel<1>, dim3((unsigned)nb), dim3(256), 0, as_stream(stream), dy, ldy, x, ldx, gamma, mean, rstd, dx, lddx, dx_bf16, ld_bf16, dgamma, rows, cols);
-    else if (cols == 512) hipLaunchKernelGGL(ln_bwd_trunk_kernel<2>, dim3((unsigned)nb), dim3(256), 0, as_stream(stream), dy, ldy, x, ldx, gamma, mean, rstd, dx, lddx, dx_bf16, ld_bf16, dgamma, rows, cols);
-    else hipLaunchKernelGGL(ln_bwd_trunk_kernel<4>, dim3((unsigned)nb), dim3(256), 0, as_stream(stream), dy, ldy, x, ldx, gamma, mean, rstd, dx, lddx, dx_bf16, ld_bf16, dgamma, rows, cols);
+    const int64_t nb = ln_bwd_trunk_blocks(rows);
+    *slots = nb;
+    if (cols == 256) hipLaunchKernelGGL((ln_bwd_trunk_kernel<1, DET>), dim3((unsigned)nb), dim3(256), 0, as_stream(stream), dy, ldy, x, ldx, gamma, mean, rstd, dx, lddx, dx_bf16, ld_bf16, dgamma, rows, cols);
+    else if (cols == 512) hipLaunchKernelGGL((ln_bwd_trunk_kernel<2, DET>), dim3((unsigned)nb), dim3(256), 0, as_stream(stream), dy, ldy, x, ldx, gamma, mean, rstd, dx, lddx, dx_bf16, ld_bf16, dgamma, rows, cols);
+    else hipLaunchKernelGGL((ln_bwd_trunk_kernel<4, DET>), dim3((unsigned)nb), dim3(256), 0, as_stream(stream), dy, ldy, x, ldx, gamma, mean, rstd, dx, lddx, dx_bf16, ld_bf16, dgamma, rows, cols);
     return launch_status();
   }
-  int64_t blocks = (rows + 3) / 4;
-  // every workgroup ends with one atomic per column on the same dgamma / dbeta / dxsum addresses, and a wavefront has one row in
-  // flight: few workgroups at few rows, up to four per CU at many (measured, tools/bench_ln_encoder.py: 3,600 rows 14.5 us at
-  // 256 against 30.7 at 1,024; 48,000 rows 134 us at 256 against 70 at 1,024)
-  int64_t bcap = rows / 32;
-  if (bcap < 256) bcap = 256;
-  if (bcap > 1024) bcap = 1024;
-  if (mca_knobs[14] > 0) bcap = mca_knobs[14];
-  if (blocks > bcap) blocks = bcap;
+  const int64_t blocks = ln_bwd_general_blocks(rows);
+  *slots = blocks;
   if (vec)
-    hipLaunchKernelGGL(ln_bwd_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), dy, ldy, y_bstride,
+    hipLaunchKernelGGL((ln_bwd_kernel<4, DET>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), dy, ldy, y_bstride,
                        period, x, ldx, gamma, mean, rstd, rowmask, dx, lddx, dx_bf16, ld_bf16, dgamma, dbeta, dxsum, rows, cols);
   else
-    hipLaunchKernelGGL(ln_bwd_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), dy, ldy, y_bstride,
+    hipLaunchKernelGGL((ln_bwd_kernel<1, DET>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), dy, ldy, y_bstride,
                        period, x, ldx, gamma, mean, rstd, rowmask, dx, lddx, dx_bf16, ld_bf16, dgamma, dbeta, dxsum, rows, cols);
   return launch_status();
+}
+
+extern "C" int mca_layernorm_bwd(const float* dy, int64_t ldy, int64_t y_bstride, int64_t period,
+                                 const float* x, int64_t ldx, const float* gamma,
+                                 const float* mean, const float* rstd, const uint8_t* rowmask,
+                                 float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16,
+                                 float* dgamma, float* dbeta, float* dxsum, int64_t rows, int cols, mca_stream_t stream) {
+  if (!dy || !x || !gamma || !mean || !rstd || rows < 0 || cols <= 0 || cols > 1024) return MCA_E_BADARG;
+  if (rows == 0) return MCA_OK;
+  int64_t slots;
+  return ln_bwd_launch<false>(dy, ldy, y_bstride, period, x, ldx, gamma, mean, rstd, rowmask, dx, lddx, dx_bf16, ld_bf16, dgamma, dbeta, dxsum,
+                              rows, cols, stream, &slots);
+}
+
+// =====================================================================================================
+// Deterministic mode: the ordered reduce every deterministic form ends with.  One thread per destination element adds
+// the slots in ascending index, sequentially in fp32, and adds the total into the destination with a plain (non-atomic)
+// read-modify-write: dst = dst + (((p_0 + p_1) + p_2) + ...).  The caller orders launches that target the same tensor.
+// =====================================================================================================
+static inline unsigned stream_grid(int64_t items);
+__global__ __launch_bounds__(256) void det_reduce_kernel(const float* __restrict__ scratch, int64_t slot_stride, int slots,
+                                                          float* __restrict__ dst, int64_t ldd, int64_t rows, int cols) {
+  const int64_t total = rows * cols;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+    const float* p = scratch + idx;
+    float sum = p[0];
+#pragma unroll 4
+    for (int s = 1; s < slots; s++) sum += p[(int64_t)s * slot_stride];
+    float* d = dst + (idx / cols) * ldd + idx % cols;
+    *d = *d + sum;
+  }
+}
+int mca_det_reduce(const float* scratch, int64_t slot_stride, int slots, float* dst, int64_t ldd, int64_t rows, int cols, mca_stream_t stream) {
+  if (!scratch || !dst || slots <= 0 || rows <= 0 || cols <= 0) return MCA_E_BADARG;
+  hipLaunchKernelGGL(det_reduce_kernel, dim3(stream_grid(rows * cols)), dim3(256), 0, as_stream(stream), scratch, slot_stride, slots, dst, ldd,
+                     rows, cols);
+  return launch_status();
+}
+
+extern "C" int64_t mca_layernorm_bwd_det_scratch(int64_t rows, int cols) {
+  if (rows <= 0 || cols <= 0 || cols > 1024) return 0;
+  int64_t slots = ln_bwd_general_blocks(rows);
+  const int64_t ps = ln_bwd_params_slabs(rows, cols, nullptr);
+  if (ps > slots) slots = ps;
+  if (cols == 256 || cols == 512 || cols == 1024) { const int64_t tb = ln_bwd_trunk_blocks(rows); if (tb > slots) slots = tb; }
+  return slots * 3 * cols;
+}
+extern "C" int mca_layernorm_bwd_det(const float* dy, int64_t ldy, int64_t y_bstride, int64_t period,
+                                     const float* x, int64_t ldx, const float* gamma,
+                                     const float* mean, const float* rstd, const uint8_t* rowmask,
+                                     float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16,
+                                     float* dgamma, float* dbeta, float* dxsum, int64_t rows, int cols,
+                                     float* scratch, int64_t scratch_floats, mca_stream_t stream) {
+  if (!dy || !x || !gamma || !mean || !rstd || rows < 0 || cols <= 0 || cols > 1024) return MCA_E_BADARG;
+  if (rows == 0) return MCA_OK;
+  if (!scratch || scratch_floats < mca_layernorm_bwd_det_scratch(rows, cols)) return MCA_E_BADARG;
+  float* part[3] = {dgamma ? scratch : nullptr, dbeta ? scratch + cols : nullptr, dxsum ? scratch + 2 * cols : nullptr};
+  float* target[3] = {dgamma, dbeta, dxsum};
+  int64_t slots = 0;
+  int rc = ln_bwd_launch<true>(dy, ldy, y_bstride, period, x, ldx, gamma, mean, rstd, rowmask, dx, lddx, dx_bf16, ld_bf16, part[0], part[1], part[2],
+                               rows, cols, stream, &slots);
+  for (int t = 0; t < 3 && rc == MCA_OK && slots > 0; t++)
+    if (target[t]) rc = mca_det_reduce(part[t], 3 * (int64_t)cols, (int)slots, target[t], cols, 1, cols, stream);
+  return rc;
 }
 
 // =====================================================================================================
@@ -662,6 +757,7 @@ extern "C" int mca_bcast_rows(const float* src, int64_t lds, float* dst, int64_t
 }
 
 // dst[(i % period), c] += sum_i src[...]: each block owns a slab of rows, one atomic per (prow, c) per block
+template <bool DET>
 __global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restrict__ src, int64_t lds,
                                                            int64_t src_bstride, int64_t period,
                                                            float* __restrict__ dst, int64_t ldd, int64_t rows,
@@ -678,12 +774,11 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restric
   for (int64_t g = g0; g < g1; g++) {
     if (g * period + prow < rows) acc += src[g * src_bstride + prow * lds + c];
   }
-  if (acc != 0.f) atomicAdd(dst + prow * ldd + c, acc);
+  if constexpr (DET) dst[((int64_t)blockIdx.z * gridDim.y + prow) * ldd + c] = acc;          // slot blockIdx.z: [period][ldd = cols]
+  else if (acc != 0.f) atomicAdd(dst + prow * ldd + c, acc);
 }
-extern "C" int mca_reduce_rows(const float* src, int64_t lds, int64_t src_bstride, int64_t period, float* dst,
-                               int64_t ldd, int64_t rows, int cols, mca_stream_t stream) {
-  if (!src || !dst || rows < 0 || cols <= 0 || period <= 0) return MCA_E_BADARG;
-  if (rows == 0) return MCA_OK;
+// slabs over the i / period index and groups per slab
+static inline int64_t reduce_rows_slabs(int64_t rows, int64_t period, int cols, int64_t* gpb_out) {
   const int64_t ngroups = (rows + period - 1) / period;
   // Two rounds of workgroups at most: every slab ends with one atomic per (prow, column), and the slabs of one column all hit
   // the same address (a bias gradient over 12,000 rows in 1,024 slabs: 38 us for 25 MB, all of it same-address atomics; knob 14
@@ -692,11 +787,37 @@ extern "C" int mca_reduce_rows(const float* src, int64_t lds, int64_t src_bstrid
   const int64_t wgs = mca_knobs[14] > 0 ? mca_knobs[14] : 512;
   int64_t slabs = wgs / per_slab > 0 ? wgs / per_slab : 1;
   if (slabs > ngroups) slabs = ngroups;
-  const int64_t gpb = (ngroups + slabs - 1) / slabs;
+  if (gpb_out) *gpb_out = (ngroups + slabs - 1) / slabs;
+  return slabs;
+}
+extern "C" int mca_reduce_rows(const float* src, int64_t lds, int64_t src_bstride, int64_t period, float* dst,
+                               int64_t ldd, int64_t rows, int cols, mca_stream_t stream) {
+  if (!src || !dst || rows < 0 || cols <= 0 || period <= 0) return MCA_E_BADARG;
+  if (rows == 0) return MCA_OK;
+  int64_t gpb;
+  const int64_t slabs = reduce_rows_slabs(rows, period, cols, &gpb);
   if (period > 65535) return MCA_E_UNSUPPORTED;
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3((cols + 255) / 256, (unsigned)period, (unsigned)slabs), dim3(256), 0,
+  hipLaunchKernelGGL(reduce_rows_kernel<false>, dim3((cols + 255) / 256, (unsigned)period, (unsigned)slabs), dim3(256), 0,
                      as_stream(stream), src, lds, src_bstride, period, dst, ldd, rows, cols, gpb);
   return launch_status();
+}
+extern "C" int64_t mca_reduce_rows_det_scratch(int64_t rows, int64_t period, int cols) {
+  if (rows <= 0 || cols <= 0 || period <= 0) return 0;
+  return reduce_rows_slabs(rows, period, cols, nullptr) * period * cols;
+}
+extern "C" int mca_reduce_rows_det(const float* src, int64_t lds, int64_t src_bstride, int64_t period, float* dst, int64_t ldd,
+                                   int64_t rows, int cols, float* scratch, int64_t scratch_floats, mca_stream_t stream) {
+  if (!src || !dst || rows < 0 || cols <= 0 || period <= 0) return MCA_E_BADARG;
+  if (rows == 0) return MCA_OK;
+  if (period > 65535) return MCA_E_UNSUPPORTED;
+  int64_t gpb;
+  const int64_t slabs = reduce_rows_slabs(rows, period, cols, &gpb);
+  if (!scratch || scratch_floats < slabs * period * cols) return MCA_E_BADARG;
+  hipLaunchKernelGGL(reduce_rows_kernel<true>, dim3((cols + 255) / 256, (unsigned)period, (unsigned)slabs), dim3(256), 0,
+                     as_stream(stream), src, lds, src_bstride, period, scratch, (int64_t)cols, rows, cols, gpb);
+  const int rc = launch_status();
+  if (rc != MCA_OK) return rc;
+  return mca_det_reduce(scratch, period * cols, (int)slabs, dst, ldd, period, cols, stream);
 }
 
 // =====================================================================================================
@@ -751,6 +872,7 @@ extern "C" int mca_tab_value_fwd(const float* x, const float* w1, const float* b
 }
 
 // dw1[d] += sum_r dh1[r][d] * [h1[r][d] > 0] * min(x[r], max_value);  db1[d] += sum_r dh1[r][d] * [h1 > 0]
+template <bool DET>
 __global__ __launch_bounds__(256) void tab_value_bwd_kernel(const float* __restrict__ dh1, int64_t ld, const u16* __restrict__ h1,
                                                              const float* __restrict__ x, float* __restrict__ dw1,
                                                              float* __restrict__ db1, int64_t rows, int cols, float max_value,
@@ -765,18 +887,45 @@ __global__ __launch_bounds__(256) void tab_value_bwd_kernel(const float* __restr
     aw += g * fminf(x[r], max_value);
     ab += g;
   }
-  atomicAdd(dw1 + c, aw);
-  atomicAdd(db1 + c, ab);
+  if constexpr (DET) {          // slot blockIdx.y: [2][cols], dw1 then db1
+    dw1[(int64_t)blockIdx.y * 2 * cols + c] = aw;
+    db1[(int64_t)blockIdx.y * 2 * cols + c] = ab;
+  } else {
+    atomicAdd(dw1 + c, aw);
+    atomicAdd(db1 + c, ab);
+  }
+}
+static inline int64_t tab_value_bwd_slabs(int64_t rows, int64_t* rpb_out) {
+  int64_t slabs = rows < 512 ? rows : 512;
+  const int64_t rpb = (rows + slabs - 1) / slabs;
+  if (rpb_out) *rpb_out = rpb;
+  return (rows + rpb - 1) / rpb;
 }
 extern "C" int mca_tab_value_bwd(const float* dh1, int64_t ld, const uint16_t* h1, const float* x, float* dw1, float* db1,
                                  int64_t rows, int cols, float max_value, mca_stream_t stream) {
   if (!dh1 || !h1 || !x || !dw1 || !db1 || rows <= 0 || cols <= 0) return MCA_E_BADARG;
-  int64_t slabs = rows < 512 ? rows : 512;
-  const int64_t rpb = (rows + slabs - 1) / slabs;
-  slabs = (rows + rpb - 1) / rpb;
-  hipLaunchKernelGGL(tab_value_bwd_kernel, dim3((cols + 255) / 256, (unsigned)slabs), dim3(256), 0, as_stream(stream), dh1, ld, h1, x,
+  int64_t rpb;
+  const int64_t slabs = tab_value_bwd_slabs(rows, &rpb);
+  hipLaunchKernelGGL(tab_value_bwd_kernel<false>, dim3((cols + 255) / 256, (unsigned)slabs), dim3(256), 0, as_stream(stream), dh1, ld, h1, x,
                      dw1, db1, rows, cols, max_value, rpb);
   return launch_status();
+}
+extern "C" int64_t mca_tab_value_bwd_det_scratch(int64_t rows, int cols) {
+  if (rows <= 0 || cols <= 0) return 0;
+  return tab_value_bwd_slabs(rows, nullptr) * 2 * cols;
+}
+extern "C" int mca_tab_value_bwd_det(const float* dh1, int64_t ld, const uint16_t* h1, const float* x, float* dw1, float* db1,
+                                     int64_t rows, int cols, float max_value, float* scratch, int64_t scratch_floats, mca_stream_t stream) {
+  if (!dh1 || !h1 || !x || !dw1 || !db1 || rows <= 0 || cols <= 0) return MCA_E_BADARG;
+  int64_t rpb;
+  const int64_t slabs = tab_value_bwd_slabs(rows, &rpb);
+  if (!scratch || scratch_floats < slabs * 2 * cols) return MCA_E_BADARG;
+  hipLaunchKernelGGL(tab_value_bwd_kernel<true>, dim3((cols + 255) / 256, (unsigned)slabs), dim3(256), 0, as_stream(stream), dh1, ld, h1, x,
+                     scratch, scratch + cols, rows, cols, max_value, rpb);
+  int rc = launch_status();
+  if (rc == MCA_OK) rc = mca_det_reduce(scratch, 2 * (int64_t)cols, (int)slabs, dw1, cols, 1, cols, stream);
+  if (rc == MCA_OK) rc = mca_det_reduce(scratch + cols, 2 * (int64_t)cols, (int)slabs, db1, cols, 1, cols, stream);
+  return rc;
 }
 
 

@@ -1013,6 +1013,10 @@ __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0); \
   }
 
+// DET (all four weight-gradient kernels): the deterministic forms' epilogue.  C is then the caller's scratch with ldc = K and
+// every row split STORES its partial tile into slot split_id (C + split_id * N * ldc) instead of adding it into C atomically;
+// det_reduce_kernel (elementwise.hip) adds the slots in ascending order.  DET = false is the code it always was.
+template <bool DET>
 __global__ __launch_bounds__(256) void gemm_tn_kernel(const u16* __restrict__ A, int64_t lda,
                                                        const u16* __restrict__ B, int64_t ldb, float* __restrict__ C,
                                                        int64_t ldc, int R, int N, int K, int tiles_k, int rows_per_split, int dbg) {
@@ -1125,8 +1129,12 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const u16* __restrict__ A,
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         const int n = n0 + wn * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (n < N && !(dbg & 1)) atomicAdd(C + (int64_t)n * ldc + k, acc[i][j][r]);
-        if ((dbg & 1) && acc[i][j][r] == 123.456f) C[0] = 1.f;
+        if constexpr (DET) {
+          if (n < N) C[((int64_t)blockIdx.y * N + n) * ldc + k] = acc[i][j][r];
+        } else {
+          if (n < N && !(dbg & 1)) atomicAdd(C + (int64_t)n * ldc + k, acc[i][j][r]);
+          if ((dbg & 1) && acc[i][j][r] == 123.456f) C[0] = 1.f;
+        }
       }
   }
 }
@@ -1138,6 +1146,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const u16* __restrict__ A,
 // ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int tn_off256(int r, int c) { return r * 256 + ((c ^ ((r & 3) << 2)) << 3); }
 
+template <bool DET>
 __global__ __launch_bounds__(512) void gemm_tn_256_kernel(const u16* __restrict__ A, int64_t lda,
                                                            const u16* __restrict__ B, int64_t ldb, float* __restrict__ C,
                                                            int64_t ldc, int R, int N, int K, int tiles_k, int rows_per_split, int dbg) {
@@ -1256,7 +1265,11 @@ __global__ __launch_bounds__(512) void gemm_tn_256_kernel(const u16* __restrict_
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         const int n = n0 + wn * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (n < N) atomicAdd(C + (int64_t)n * ldc + k, acc[i][j][r]);
+        if constexpr (DET) {
+          if (n < N) C[((int64_t)split_id * N + n) * ldc + k] = acc[i][j][r];          // split_id: the LOGICAL split (after xcd_remap)
+        } else {
+          if (n < N) atomicAdd(C + (int64_t)n * ldc + k, acc[i][j][r]);
+        }
       }
   }
 }
@@ -1268,6 +1281,7 @@ __global__ __launch_bounds__(512) void gemm_tn_256_kernel(const u16* __restrict_
 // 256x128.  8 wavefronts as 4 (n) x 2 (k), each 64 x 128 = 2 x 4 accumulators (128 VGPRs); FIVE LDS stages of
 // 32 rows (160 KiB), DMA four steps ahead; fragments by ds_read_b64_tr_b16 (12 per k16-step for 8 MFMAs).
 // ---------------------------------------------------------------------------------------------------------
+template <bool DET>          // DET: C is this (tile, split) cell's slot, stored; else the gradient, added atomically
 __device__ __forceinline__ void tn_256x256_tile(const u16* __restrict__ A, int64_t lda, const u16* __restrict__ B, int64_t ldb,
                                                 float* __restrict__ C, int64_t ldc, int N, int K, int tn, int tk, int r_begin,
                                                 int r_end, u16* ldst) {
@@ -1413,11 +1427,16 @@ __device__ __forceinline__ void tn_256x256_tile(const u16* __restrict__ A, int64
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         const int n = n0 + wn * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (n < N) atomicAdd(C + (int64_t)n * ldc + k, acc[i][j][r]);
+        if constexpr (DET) {
+          if (n < N) C[(int64_t)n * ldc + k] = acc[i][j][r];
+        } else {
+          if (n < N) atomicAdd(C + (int64_t)n * ldc + k, acc[i][j][r]);
+        }
       }
   }
 }
 
+template <bool DET>
 __global__ __launch_bounds__(512) void gemm_tn_256x256_kernel(const u16* __restrict__ A, int64_t lda,
                                                                const u16* __restrict__ B, int64_t ldb, float* __restrict__ C,
                                                                int64_t ldc, int R, int N, int K, int tiles_k, int rows_per_split, int dbg) {
@@ -1427,7 +1446,7 @@ __global__ __launch_bounds__(512) void gemm_tn_256x256_kernel(const u16* __restr
   const int tile_id = lin % (int)gridDim.x, split_id = lin / (int)gridDim.x;
   const int r_begin = split_id * rows_per_split;
   int r_end = r_begin + rows_per_split; if (r_end > R) r_end = R;
-  tn_256x256_tile(A, lda, B, ldb, C, ldc, N, K, tile_id / tiles_k, tile_id % tiles_k, r_begin, r_end, ldst);
+  tn_256x256_tile<DET>(A, lda, B, ldb, DET ? C + (int64_t)split_id * N * ldc : C, ldc, N, K, tile_id / tiles_k, tile_id % tiles_k, r_begin, r_end, ldst);
 }
 
 // Several weight gradients over the SAME token rows in one launch (the four of a transformer layer): the launch then has
@@ -1444,6 +1463,9 @@ struct tn_group {
   int unit, n_full, span;          // the balanced row partition: mca_tn_partition (gemm_plan.h), planned by mca_plan_gemm_tn_group
   int own;
 };
+// DET: the uniform partition only (n_full splits, no line: every workgroup is one (tile, split) cell); g.C[p] / g.ldc[p] are member
+// p's place in slot 0 of the scratch; a slot is the members' packed partials one after the other
+template <bool DET>
 __global__ __launch_bounds__(512) void gemm_tn_256x256_group_kernel(tn_group g, int dbg) {
   extern __shared__ __attribute__((aligned(16))) u16 ldst[];
   const int lin0 = (int)blockIdx.x;
@@ -1468,6 +1490,11 @@ __global__ __launch_bounds__(512) void gemm_tn_256x256_group_kernel(tn_group g, 
     e = s + g.span;
     const int64_t line = (int64_t)(g.tiles - line0) * rest;
     if (e > line) e = line;
+  }
+  int64_t slot_stride = 0;          // floats from one split's slot to the next
+  if constexpr (DET) {
+#pragma unroll
+    for (int i = 0; i < MCA_TN_MAX_GROUP; i++) if (i < g.n) slot_stride += (int64_t)g.N[i] * g.K[i];
   }
   bool first = true;
   for (;;) {
@@ -1495,8 +1522,8 @@ __global__ __launch_bounds__(512) void gemm_tn_256x256_group_kernel(tn_group g, 
     const int tile_id = tile_all - g.first_tile[p];
     if (!first) __syncthreads();          // the previous segment's last fragment reads, before this one's DMA lands in the ring
     first = false;
-    tn_256x256_tile(g.A[p], g.lda[p], g.B[p], g.ldb[p], g.C[p], g.ldc[p], g.N[p], g.K[p], tile_id / g.tiles_k[p], tile_id % g.tiles_k[p],
-                    r_begin, r_end, ldst);
+    tn_256x256_tile<DET>(g.A[p], g.lda[p], g.B[p], g.ldb[p], DET ? g.C[p] + (int64_t)(lin / g.tiles) * slot_stride : g.C[p], g.ldc[p], g.N[p], g.K[p],
+                         tile_id / g.tiles_k[p], tile_id % g.tiles_k[p], r_begin, r_end, ldst);
     if (lin < n_cells) break;
   }
 #ifdef MCA_TRACE_BUILD
@@ -1579,12 +1606,22 @@ static int launch(const mca_gemm_plan& p, const gemm_operands& o, mca_stream_t s
     case MCA_GK_NT_PERSIST_GEGLU_FWD: return launch_persist<4, false>(p, o, s);
     case MCA_GK_NT_PERSIST256: return launch_persist256<false>(p, o, s);
     case MCA_GK_NT_PERSIST256_GEGLU_FWD: return launch_persist256<true>(p, o, s);
-    case MCA_GK_TN: return launch_tn<gemm_tn_kernel>(p, o, s);
-    case MCA_GK_TN_256: return launch_tn<gemm_tn_256_kernel>(p, o, s);
-    case MCA_GK_TN_256X256: return launch_tn<gemm_tn_256x256_kernel>(p, o, s);
-    case MCA_GK_TN_256X256_GROUP: return launch_kernel<gemm_tn_256x256_group_kernel>(p, s, *o.group, p.dbg);
+    case MCA_GK_TN: return launch_tn<gemm_tn_kernel<false>>(p, o, s);
+    case MCA_GK_TN_256: return launch_tn<gemm_tn_256_kernel<false>>(p, o, s);
+    case MCA_GK_TN_256X256: return launch_tn<gemm_tn_256x256_kernel<false>>(p, o, s);
+    case MCA_GK_TN_256X256_GROUP: return launch_kernel<gemm_tn_256x256_group_kernel<false>>(p, s, *o.group, p.dbg);
   }
   return MCA_E_LAUNCH;          // a plan without a kernel is a missing kernel, never a quiet no-op
+}
+// the deterministic instantiations of the four weight-gradient kernels (o.C: the scratch, o.ldc: K)
+static int launch_det(const mca_gemm_plan& p, const gemm_operands& o, mca_stream_t s) {
+  switch (p.kernel) {
+    case MCA_GK_TN: return launch_tn<gemm_tn_kernel<true>>(p, o, s);
+    case MCA_GK_TN_256: return launch_tn<gemm_tn_256_kernel<true>>(p, o, s);
+    case MCA_GK_TN_256X256: return launch_tn<gemm_tn_256x256_kernel<true>>(p, o, s);
+    case MCA_GK_TN_256X256_GROUP: return launch_kernel<gemm_tn_256x256_group_kernel<true>>(p, s, *o.group, p.dbg);
+  }
+  return MCA_E_LAUNCH;
 }
 
 static uint64_t addr(const void* p) { return (uint64_t)(uintptr_t)p; }
@@ -1701,6 +1738,80 @@ extern "C" int mca_gemm_tn_acc_group(const mca_tn_desc* d, int n, int64_t R, mca
   return launch(p.launch, o, stream);
 }
 
+// ---- deterministic forms (include/mca_hip.h, "Deterministic mode"): partial slabs into the caller's scratch, then the ordered reduce
+extern "C" int64_t mca_gemm_tn_acc_det_scratch(int64_t R, int64_t N, int64_t K) {
+  if (R <= 0 || N <= 0 || K <= 0 || R > (1LL << 30)) return 0;
+  return mca_plan_gemm_tn_det(R, N, K, mca_knobs).scratch_floats;
+}
+extern "C" int64_t mca_gemm_tn_acc_group_det_scratch(const int64_t* N, const int64_t* K, int n, int64_t R, int cus) {
+  if (!N || !K || n <= 0 || n > MCA_TN_MAX_GROUP || R <= 0 || R > (1LL << 30)) return 0;
+  return mca_plan_gemm_tn_group_det(N, K, n, R, mca_knobs, cus > 0 ? cus : num_cus()).scratch_floats;
+}
+
+extern "C" int mca_gemm_tn_acc_det(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, float* C, int64_t ldc,
+                                   int64_t R, int64_t N, int64_t K, float* scratch, int64_t scratch_floats, mca_stream_t stream) {
+  if (R <= 0) return MCA_E_BADARG;
+  int rc = check_tn(A, lda, B, ldb, C, ldc, N, K);
+  if (rc != MCA_OK) return rc;
+  if (R > (1LL << 30)) return MCA_E_UNSUPPORTED;
+  const mca_tn_det_plan p = mca_plan_gemm_tn_det(R, N, K, mca_knobs);
+  if (p.slots <= 1) return mca_gemm_tn_acc(A, lda, B, ldb, C, ldc, R, N, K, stream);          // one contributor per element
+  if (!scratch || scratch_floats < p.scratch_floats) return MCA_E_BADARG;
+  const gemm_operands o = {A, lda, B, ldb, scratch, K, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, (int)R, (int)K, nullptr};
+  rc = launch_det(p.launch, o, stream);
+  if (rc != MCA_OK) return rc;
+  return mca_det_reduce(scratch, p.slot_stride, p.slots, C, ldc, N, (int)K, stream);
+}
+
+extern "C" int mca_gemm_tn_acc_group_det(const mca_tn_desc* d, int n, int64_t R, float* scratch, int64_t scratch_floats, mca_stream_t stream) {
+  if (!d || n <= 0 || n > MCA_TN_MAX_GROUP || R <= 0) return MCA_E_BADARG;
+  if (R > (1LL << 30)) return MCA_E_UNSUPPORTED;
+  int64_t Ns[MCA_TN_MAX_GROUP], Ks[MCA_TN_MAX_GROUP];
+  for (int i = 0; i < n; i++) {
+    const int rc = check_tn(d[i].A, d[i].lda, d[i].B, d[i].ldb, d[i].C, d[i].ldc, d[i].N, d[i].K);
+    if (rc != MCA_OK) return rc;
+    Ns[i] = d[i].N; Ks[i] = d[i].K;
+  }
+  const mca_tn_group_det_plan p = mca_plan_gemm_tn_group_det(Ns, Ks, n, R, mca_knobs, num_cus());
+  if (p.plan.grouped < 0) return p.plan.grouped;
+  if (p.scratch_floats > 0 && (!scratch || scratch_floats < p.scratch_floats)) return MCA_E_BADARG;          // before anything is launched
+  if (!p.plan.grouped) {          // one deterministic launch per member; stream order lets them share the scratch
+    for (int i = 0; i < n; i++) {
+      const int rc = mca_gemm_tn_acc_det(d[i].A, d[i].lda, d[i].B, d[i].ldb, d[i].C, d[i].ldc, R, d[i].N, d[i].K, scratch, scratch_floats, stream);
+      if (rc != MCA_OK) return rc;
+    }
+    return MCA_OK;
+  }
+  const bool det = p.slots > 1;          // one split: the plain kernel over the same partition, one contributor per element
+  tn_group g;
+  int tiles = 0;
+  int64_t off = 0;
+  for (int i = 0; i < n; i++) {
+    g.A[i] = d[i].A; g.B[i] = d[i].B;
+    g.C[i] = det ? scratch + off : d[i].C;
+    g.lda[i] = d[i].lda; g.ldb[i] = d[i].ldb; g.ldc[i] = det ? d[i].K : d[i].ldc;
+    g.N[i] = (int)d[i].N; g.K[i] = (int)d[i].K;
+    g.tiles_k[i] = (int)((d[i].K + 255) / 256);
+    g.first_tile[i] = tiles;
+    tiles += mca_tn_group_member_tiles(d[i].N, d[i].K);
+    off += d[i].N * d[i].K;
+  }
+  for (int i = n; i <= MCA_TN_MAX_GROUP; i++) g.first_tile[i] = tiles;
+  g.n = n; g.R = p.plan.part.R; g.tiles = p.plan.part.tiles;
+  g.unit = p.plan.part.unit; g.n_full = p.plan.part.n_full; g.span = p.plan.part.span; g.own = p.plan.part.own;
+  gemm_operands o = {};
+  o.group = &g;
+  int rc = det ? launch_det(p.plan.launch, o, stream) : launch(p.plan.launch, o, stream);
+  if (rc != MCA_OK || !det) return rc;
+  off = 0;
+  for (int i = 0; i < n; i++) {
+    rc = mca_det_reduce(scratch + off, p.slot_stride, p.slots, d[i].C, d[i].ldc, d[i].N, (int)d[i].K, stream);
+    if (rc != MCA_OK) return rc;
+    off += d[i].N * d[i].K;
+  }
+  return MCA_OK;
+}
+
 // ---- the plans themselves, for tests and tools (include/mca_hip_debug.h): the planners the entry points above call, with
 // the current knob table; cus = 0 asks the runtime.  Nothing is launched and no device is touched.
 extern "C" int mca_dbg_plan_gemm_nt(int entry, const mca_nt_problem* pr, int cus, mca_gemm_plan* out) {
@@ -1732,5 +1843,15 @@ extern "C" int mca_dbg_plan_gemm_tn_group(const int64_t* N, const int64_t* K, in
     tiles += t;
   }
   *out = mca_plan_gemm_tn_group(all_taken ? tiles : 0, n, R, mca_knobs, cus > 0 ? cus : num_cus());
+  return MCA_OK;
+}
+extern "C" int mca_dbg_plan_gemm_tn_det(int64_t R, int64_t N, int64_t K, mca_tn_det_plan* out) {
+  if (!out || R <= 0 || N <= 0 || K <= 0) return MCA_E_BADARG;
+  *out = mca_plan_gemm_tn_det(R, N, K, mca_knobs);
+  return MCA_OK;
+}
+extern "C" int mca_dbg_plan_gemm_tn_group_det(const int64_t* N, const int64_t* K, int n, int64_t R, int cus, mca_tn_group_det_plan* out) {
+  if (!N || !K || !out || n <= 0 || n > MCA_TN_MAX_GROUP || R <= 0) return MCA_E_BADARG;
+  *out = mca_plan_gemm_tn_group_det(N, K, n, R, mca_knobs, cus > 0 ? cus : num_cus());
   return MCA_OK;
 }

@@ -369,3 +369,76 @@ static inline void mca_tn_group_segments(const mca_tn_partition& g, int lin, Emi
     if (lin < n_cells) break;
   }
 }
+
+// ======================================================================================================================
+// Deterministic forms (mca_gemm_tn_acc_det, mca_gemm_tn_acc_group_det): the same tiles and row splits, but every split
+// STORES its whole [N, K] partial into a slot of its own of the caller's scratch (slot = logical split index), and one
+// reduce launch then adds the slots in ascending order into C.  The plans below say how many slots there are, how far
+// apart they lie and how much scratch that takes.  slots == 1: one contributor per element already - the plain kernel
+// runs (its one atomic add per element is dst + p_0) and no scratch is needed.
+// ======================================================================================================================
+struct mca_tn_det_plan {
+  mca_gemm_plan launch;            // mca_plan_gemm_tn's launch, unchanged: grid_x tiles, grid_y = slots row splits
+  int slots;                       // partial slabs [N, K] (packed, leading dimension K), slot s at scratch + s * slot_stride
+  int64_t slot_stride;             // N * K floats
+  int64_t scratch_floats;          // slots * slot_stride; 0 when slots == 1
+};
+
+static inline mca_tn_det_plan mca_plan_gemm_tn_det(int64_t R, int64_t N, int64_t K, const int* knobs) {
+  mca_tn_det_plan d = {};
+  d.launch = mca_plan_gemm_tn(R, N, K, knobs);
+  d.slots = d.launch.grid_y;
+  d.slot_stride = N * K;
+  d.scratch_floats = d.slots > 1 ? d.slots * d.slot_stride : 0;
+  return d;
+}
+
+// A group: the uniform-split partition the default planner has behind knob 3 (n_full = S cells of `unit` rows per tile, no
+// tile-major line, no owner segments), so that every (tile, split) cell has exactly ONE workgroup and a slot is a split.
+// S: the whole rounds of workgroups one per CU that the tiles allow, cus / tiles - what the default plan takes as n_full
+// before it deals the remaining CUs out as spans; the deterministic form leaves those CUs idle instead (a span's partial
+// would need a slot whose position depends on the balance).  At least 4 steps of 32 rows per cell, at least 1 split;
+// knob 3 > 0 sets S as it sets the splits everywhere else.  A slot holds the members' [N_i, K_i] partials one after the
+// other (member i at sum_{j < i} N_j * K_j, packed).  plan.grouped == 0: the default planner refuses the group (few rows,
+// one member, few tiles, knob 11): one single-problem deterministic launch per member, each reusing the scratch, whose
+// need is then the largest member's.
+struct mca_tn_group_det_plan {
+  mca_tn_group_plan plan;          // grouped == 1: part.n_full == slots, part.span == part.own == 0
+  int slots;
+  int64_t slot_stride;             // sum of N_i * K_i
+  int64_t scratch_floats;
+};
+
+static inline mca_tn_group_det_plan mca_plan_gemm_tn_group_det(const int64_t* N, const int64_t* K, int n, int64_t R, const int* knobs, int cus) {
+  mca_tn_group_det_plan d = {};
+  int tiles = 0;
+  bool all_taken = true;
+  for (int i = 0; i < n; i++) {
+    const int t = mca_tn_group_member_tiles(N[i], K[i]);
+    all_taken = all_taken && t > 0;
+    tiles += t;
+    d.slot_stride += N[i] * K[i];
+  }
+  if (!all_taken) tiles = 0;
+  int kn[16];
+  for (int i = 0; i < 16; i++) kn[i] = knobs[i];
+  if (kn[3] <= 0) {
+    int64_t s = tiles > 0 ? cus / tiles : 1;
+    const int64_t max_s = R / (4 * BR2);
+    if (s > max_s) s = max_s;
+    if (s < 1) s = 1;
+    kn[3] = (int)s;
+  }
+  d.plan = mca_plan_gemm_tn_group(tiles, n, R, kn, cus);
+  if (d.plan.grouped == 1) {
+    d.slots = d.plan.part.n_full;
+    d.scratch_floats = d.slots > 1 ? d.slots * d.slot_stride : 0;
+  } else if (d.plan.grouped == 0) {
+    d.slots = 0; d.slot_stride = 0;
+    for (int i = 0; i < n; i++) {
+      const mca_tn_det_plan m = mca_plan_gemm_tn_det(R, N[i], K[i], knobs);
+      if (m.scratch_floats > d.scratch_floats) d.scratch_floats = m.scratch_floats;
+    }
+  }
+  return d;
+}

@@ -19,6 +19,7 @@ from __future__ import annotations
 import os
 
 import ctypes as C
+import weakref
 import math
 from typing import Callable, Dict, List, Optional
 
@@ -45,9 +46,10 @@ def debug_options() -> dict:
     weight gradient instead of one per layer), mask_mfma=0 (element-wise attention mask instead of the mask product),
     dkv_keys=256 (8-wavefront key blocks in the dK/dV pass), lazy_softmax=0 (the textbook running-maximum recurrence in the forward
     attention instead of MCA_ATTN_LAZY_REFERENCE, the default since round 5: -9 % on that kernel, statistically indistinguishable
-    from the textbook form over 8 data seeds, profiles/r05_lazy_softmax_seed_study.txt).  Kernel-level knobs: include/mca_hip_debug.h (hip.knobs)."""
+    from the textbook form over 8 data seeds, profiles/r05_lazy_softmax_seed_study.txt), deterministic=1 (the fixed-order forms of
+    the weight-gradient, LayerNorm-backward and row-reduction launches: FusionEngine.set_deterministic).  Kernel-level knobs: include/mca_hip_debug.h (hip.knobs)."""
     opts = {"overlap_wgrad": None, "group_wgrad": True, "mask_mfma": True, "dkv_keys": 128, "lazy_softmax": True,
-            "onepass": None}          # onepass=0|1: the one-pass attention backward (attention_bwd1.hip); default: by size
+            "onepass": None, "deterministic": False}          # onepass=0|1: the one-pass attention backward (attention_bwd1.hip); default: by size
     for item in filter(None, os.environ.get("MCA_DEBUG", "").split(",")):
         k, _, v = item.partition("=")
         k = k.strip()
@@ -111,6 +113,10 @@ class FusionEngine:
         # CUs) the side stream still pays in the eager loop (8.7-8.8 against 9.5-10.2 ms).  MCA_DEBUG=overlap_wgrad=0|1 forces it.
         self.overlap_wgrad = self.dbg["overlap_wgrad"]
         self.group_wgrad = self.dbg["group_wgrad"]          # one weight-gradient launch per layer
+        # Deterministic mode: every parameter gradient that is a sum over token rows is added in a fixed order
+        # (the *_det entry points of include/mca_hip.h), so a step is the same bits every time.  Off by default.
+        self._deterministic = bool(self.dbg["deterministic"])
+        self._captured = weakref.WeakSet()                  # live graph.GraphedStep objects: they replay the mode they captured
 
     # ------------------------------------------------------------------------------------------------
     # parameters -> one flat buffer (and one for gradients)
@@ -233,6 +239,25 @@ class FusionEngine:
         d = dst[dst_row0:, dst_col0:]
         rp, cp = (c, r) if transpose else (r, c)
         self._cast_list.append(hip.CastDesc(ptr(src), ptr(d), src.stride(0), r, c, dst.stride(0), rp, cp, int(transpose), float(scale)))
+
+    @property
+    def deterministic(self) -> bool:
+        return self._deterministic
+
+    def set_deterministic(self, on: bool):
+        """Deterministic mode on / off from the next step on.  A captured step replays the launches of the mode it was captured
+        in, so the mode cannot change while a GraphedStep of this engine is alive."""
+        on = bool(on)
+        if on == self._deterministic:
+            return
+        if len(self._captured):
+            raise RuntimeError("set_deterministic: a GraphedStep captured with deterministic="
+                               f"{self._deterministic} is alive and would go on replaying that mode; delete it first")
+        self._deterministic = on
+        if on:
+            for ws in self._ws.values():
+                if isinstance(ws, dict) and "T" in ws:
+                    self._alloc_det_scratch(ws)
 
     def set_attention_dtype(self, dtype: str):
         """'bf16' (default) or 'fp8' (BASELINE configs[4]): the fusion layers' forward attention computes Q K^T and P V on the
@@ -415,8 +440,85 @@ class FusionEngine:
                 ws["enc"][name] = dict(h1_b=bf(rows, D), y=f32(rows, D), m2=f32(rows), r2=f32(rows), dy=f32(rows, D),
                                        dy_b=bf(rows, D), dh1=f32(rows, D), mask=u8(rows))
         ws["side"], ws["side_events"] = torch.cuda.Stream(device=dev), []          # side stream of the weight-gradient GEMMs
+        if self._deterministic:
+            self._alloc_det_scratch(ws)
         self._ws[b] = ws
         return ws
+
+    # ------------------------------------------------------------------------------------------------
+    # deterministic mode: scratch and the *_det launches
+    # ------------------------------------------------------------------------------------------------
+    def _det_need(self, b: int) -> int:
+        """floats of scratch the largest deterministic launch of a b-sample backward needs: the library's size queries over
+        every call site of _backward_part, _backward_layers_and_encoders and _backward_tabular (grouped AND single forms of
+        the weight gradients, so the figure holds whatever group_wgrad says)"""
+        L, D, I, R, F, N, T = hip.lib(), self.D, self.I, self.R, self.F, self.N, b * self.N
+        tn = [(b * R, D, D), (R, D, D), (T, 2 * D, D), (T, D, I), (T, I, D), (T, D, D), (T, 3 * D, D)]
+        ln, rr, tab = [(T, D)], [(b * R, R), (R, R)] + ([(b * F, F)] if F else []), []
+        for mi, name in enumerate(self.model.modality_types):
+            enc, rows = self.model.encoders[name], b * self.st.token_dims[mi]
+            if isinstance(enc, EmbeddedSequenceEncoder):
+                tn.append((rows, D, enc.input_size)); ln += [(rows, D), (rows, enc.input_size)]
+            elif isinstance(enc, TabularEncoder):
+                tn.append((rows, D, D)); ln.append((rows, D)); rr.append((rows, self.st.token_dims[mi])); tab.append(rows)
+        need = max(L.mca_gemm_tn_acc_det_scratch(*t) for t in tn)
+        members = [(3 * D, D), (I, D), (I, D), (D, I), (D, D)]
+        for ms in (members, members + [(2 * D, D)]):
+            Ns, Ks = (C.c_int64 * len(ms))(*[m[0] for m in ms]), (C.c_int64 * len(ms))(*[m[1] for m in ms])
+            need = max(need, L.mca_gemm_tn_acc_group_det_scratch(Ns, Ks, len(ms), T, 0))
+        need = max([need] + [L.mca_layernorm_bwd_det_scratch(r, c) for r, c in ln] + [L.mca_reduce_rows_det_scratch(r, p, D) for r, p in rr]
+                   + [L.mca_tab_value_bwd_det_scratch(r, D) for r in tab])
+        return int(need)
+
+    def _alloc_det_scratch(self, ws):
+        """One region per stream: the weight-gradient GEMMs run on the workspace's side stream beside main-stream LayerNorm
+        launches when overlap_on(ws).  Calls on one stream share their region: stream order puts a call's reduce launch before
+        the next call's partial stores."""
+        if "det" not in ws:
+            n = max(self._det_need(ws["b"]), 1)
+            ws["det"] = {k: torch.empty(n, dtype=torch.float32, device=self.device) for k in ("main", "side")}
+
+    def _det_scratch(self, ws, need: int):
+        reg = ws["det"]["side" if hip._STREAM_CACHE is not None and hip._STREAM_CACHE == ws["side"].cuda_stream else "main"]
+        assert need <= reg.numel(), f"deterministic scratch: a launch needs {need} floats, the workspace holds {reg.numel()}"
+        return reg
+
+    def _tn(self, ws, A, B, Cgrad, R, N, K):
+        """gemm_tn_acc, or its fixed-order form in deterministic mode"""
+        if not self._deterministic:
+            return self.gemm_tn_acc(A, B, Cgrad, R, N, K)
+        s = self._det_scratch(ws, hip.lib().mca_gemm_tn_acc_det_scratch(R, N, K))
+        call("mca_gemm_tn_acc_det", ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(Cgrad), Cgrad.stride(0), R, N, K, ptr(s), s.numel(),
+             stream_ptr(), flops=2.0 * R * N * K)
+
+    def _tn_group(self, ws, members, R):
+        if not self._deterministic:
+            return self.gemm_tn_acc_group(members, R)
+        arr = (hip.TnDesc * len(members))()
+        fl = 0.0
+        for d, (A, B, Cg, N, K) in zip(arr, members):
+            d.A, d.lda, d.B, d.ldb, d.C, d.ldc, d.N, d.K = ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(Cg), Cg.stride(0), N, K
+            fl += 2.0 * R * N * K
+        Ns, Ks = (C.c_int64 * len(members))(*[m[3] for m in members]), (C.c_int64 * len(members))(*[m[4] for m in members])
+        s = self._det_scratch(ws, hip.lib().mca_gemm_tn_acc_group_det_scratch(Ns, Ks, len(members), R, 0))
+        call("mca_gemm_tn_acc_group_det", C.byref(arr), len(members), R, ptr(s), s.numel(), stream_ptr(), flops=fl)
+
+    def _ln_bwd(self, ws, dy, ldy, x, gamma, mean, rstd, rows, cols, dgamma, dbeta=None, rowmask=None, dx=None, dx_bf16=None,
+                y_bstride=0, period=0, dxsum=None):
+        if not self._deterministic:
+            return self.ln_bwd(dy, ldy, x, gamma, mean, rstd, rows, cols, dgamma, dbeta=dbeta, rowmask=rowmask, dx=dx, dx_bf16=dx_bf16,
+                               y_bstride=y_bstride, period=period, dxsum=dxsum)
+        s = self._det_scratch(ws, hip.lib().mca_layernorm_bwd_det_scratch(rows, cols))
+        call("mca_layernorm_bwd_det", ptr(dy), ldy, y_bstride, period, ptr(x), x.stride(0), ptr(gamma), ptr(mean), ptr(rstd),
+             ptr(rowmask), ptr(dx), dx.stride(0) if dx is not None else 0, ptr(dx_bf16),
+             dx_bf16.stride(0) if dx_bf16 is not None else 0, ptr(dgamma), ptr(dbeta), ptr(dxsum), rows, cols, ptr(s), s.numel(), stream_ptr())
+
+    def _reduce_rows(self, ws, src, lds, src_bstride, period, dst, ldd, rows, cols):
+        """src, dst: device addresses"""
+        if not self._deterministic:
+            return call("mca_reduce_rows", src, lds, src_bstride, period, dst, ldd, rows, cols, stream_ptr())
+        s = self._det_scratch(ws, hip.lib().mca_reduce_rows_det_scratch(rows, period, cols))
+        call("mca_reduce_rows_det", src, lds, src_bstride, period, dst, ldd, rows, cols, ptr(s), s.numel(), stream_ptr())
 
     # ------------------------------------------------------------------------------------------------
     # thin kernel wrappers
@@ -801,7 +903,19 @@ class FusionEngine:
         # Weight-gradient GEMMs (mca_gemm_tn_acc) only feed the optimizer: they are issued on a side stream, ordered after
         # the kernel that produced their operand, and run concurrently with the rest of the backward chain (their
         # operands live in per-layer buffers, so nothing overwrites them).  slot = unique id of the call site.
-        side, tn = self._on_side, self.gemm_tn_acc
+        # Deterministic mode, ordering audit.  A *_det launch adds into its gradient tensor with a plain read-modify-write, so two
+        # launches into one tensor must be ordered.  The tensors that receive more than one launch's contribution per backward:
+        #   m.norm.gamma / ly.norm.gamma (both LayerNorms of a layer), return_tokens (two mca_reduce_rows), fusion_tokens, the
+        #   encoder norms' gamma / beta and the Linear biases fed by dxsum, the embedding table, linear1.weight / bias
+        #     - all launched from this thread on the CURRENT stream: stream order;
+        #   every weight matrix (one launch each; feedforward[0].weight two launches into disjoint row blocks, or two members
+        #   of one grouped launch) - all on the side stream when overlap_on(ws), else on the current stream: stream order.
+        # No tensor gets contributions from both streams, and neighbours in the flat buffer never share an element.
+        # backward(accumulate=True): backward() ends with current.wait_stream(side) and every side launch waits for an event
+        # recorded on the current stream, so the second backward's launches follow the first's on either stream.  Nothing has
+        # to be added for deterministic mode; the scratch regions are per stream for the same reason (_alloc_det_scratch).
+        side = self._on_side
+        tn = lambda *a: self._tn(ws, *a)
         slot = [0]
 
         def on_side(fn):
@@ -810,17 +924,17 @@ class FusionEngine:
         if self.eao:
             return self._backward_part_eao(ws, dpool, bucket_ready, on_side)
         # pooled = op @ Wo^T + return_tokens
-        call("mca_reduce_rows", ptr(dpool), D, R * D, R, ptr(G(m.return_tokens)), D, b * R, D, stream_ptr())
+        self._reduce_rows(ws, ptr(dpool), D, R * D, R, ptr(G(m.return_tokens)), D, b * R, D)
         call("mca_f32_to_bf16", ptr(dpool), D, ptr(ws["dpool_b"]), D, b * R, D, 1.0, stream_ptr())
         self.gemm_nt(ws["dpool_b"], self.wp["oT"], ws["dop"], b * R, D, D)
         on_side(lambda: tn(ws["dpool_b"], ws["op"], G(ap.to_out.weight), b * R, D, D))
         # pooling attention
         self.attn_backward(*self.pool_attention(ws), ws)
         ws["dqp_sum"].zero_()
-        call("mca_reduce_rows", ptr(ws["dqp32"]), D, R * D, R, ptr(ws["dqp_sum"]), D, b * R, D, stream_ptr())
+        self._reduce_rows(ws, ptr(ws["dqp32"]), D, R * D, R, ptr(ws["dqp_sum"]), D, b * R, D)
         call("mca_f32_to_bf16", ptr(ws["dqp_sum"]), D, ptr(ws["dqp_b"]), D, R, D, 1.0, stream_ptr())
         self.gemm_nt(ws["dqp_b"], self.wp["qT"], ws["drt"], R, D, D)                 # d return_tokens via to_q
-        call("mca_reduce_rows", ptr(ws["drt"]), D, R * D, R, ptr(G(m.return_tokens)), D, R, D, stream_ptr())
+        self._reduce_rows(ws, ptr(ws["drt"]), D, R * D, R, ptr(G(m.return_tokens)), D, R, D)
         on_side(lambda: tn(ws["dqp_b"], ws["rt_b"], G(ap.to_q.weight), R, D, D))
         pool_kv = (ws["dkvp"], ws["t_b"], G(ap.to_kv.weight), 2 * D, D)
         if not (self.L > 0 and self.group_wgrad and T >= 4096):          # else: a member of the top layer's grouped launch
@@ -829,7 +943,7 @@ class FusionEngine:
         dx, dx_other = ws["dxa"], ws["dxb"]
         self.gemm_nt(ws["dkvp"], self.wp["kvT"], dx, T, D, 2 * D)                    # d (final-normed tokens), fp32
         top = ws["layers"][self.L - 1]["dxo_b"] if self.L else ws["dx_b"]
-        self.ln_bwd(dx, D, ws["x"][self.L], m.norm.gamma, ws["mf"], ws["rf"], T, D, G(m.norm.gamma), dx=dx_other, dx_bf16=top)
+        self._ln_bwd(ws, dx, D, ws["x"][self.L], m.norm.gamma, ws["mf"], ws["rf"], T, D, G(m.norm.gamma), dx=dx_other, dx_bf16=top)
         dx, dx_other = dx_other, dx
         on_side(lambda: bucket_ready(0))
         self._backward_layers_and_encoders(ws, dx, dx_other, bucket_ready, on_side, extra_top=pool_kv)
@@ -841,7 +955,7 @@ class FusionEngine:
         call("mca_segment_mean_bwd", ptr(dpool), ptr(ws["padding"]), ptr(self.kgroup), ptr(ws["seg_counts"]), R, ptr(dx), b, N, D,
              stream_ptr())
         top = ws["layers"][self.L - 1]["dxo_b"] if self.L else ws["dx_b"]
-        self.ln_bwd(dx, D, ws["x"][self.L], m.norm.gamma, ws["mf"], ws["rf"], T, D, self.grad_of(m.norm.gamma), dx=dx_other, dx_bf16=top)
+        self._ln_bwd(ws, dx, D, ws["x"][self.L], m.norm.gamma, ws["mf"], ws["rf"], T, D, self.grad_of(m.norm.gamma), dx=dx_other, dx_bf16=top)
         dx, dx_other = dx_other, dx
         on_side(lambda: bucket_ready(0))
         self._backward_layers_and_encoders(ws, dx, dx_other, bucket_ready, on_side)
@@ -849,7 +963,7 @@ class FusionEngine:
     def _backward_layers_and_encoders(self, ws, dx, dx_other, bucket_ready, on_side, extra_top=None):
         m, D, N, H, Ip, I, R, b, T = self.model, self.D, self.N, self.H, self.Ip, self.I, self.R, ws["b"], ws["T"]
         G = self.grad_of
-        tn = self.gemm_tn_acc
+        tn = lambda *a: self._tn(ws, *a)
         for bi, i in enumerate(reversed(range(self.L))):
             ly, w, a = m.layers[i], self.wl[i], ws["layers"][i]
             g = ly.norm.gamma
@@ -873,7 +987,7 @@ class FusionEngine:
             if not grouped:
                 on_side(lambda dh=dh, a=a, gw1=gw1: (tn(dh, a["x1n_b"], gw1, T, I, D), tn(dh[:, Ip:], a["x1n_b"], gw1[I:], T, I, D)))
             self.gemm_nt(dh, w["w1T"], dx_other, T, D, 2 * Ip, residual=dx)            # d x1n = dh @ W1 + dx
-            self.ln_bwd(dx_other, D, a["x1"], g, a["m2"], a["r2"], T, D, G(g), dx=dx, dx_bf16=dx1)   # dx = d x1
+            self._ln_bwd(ws, dx_other, D, a["x1"], g, a["m2"], a["r2"], T, D, G(g), dx=dx, dx_bf16=dx1)   # dx = d x1
             # x1 = o @ Wo^T + xn
             if not grouped:
                 on_side(lambda dx1=dx1, a=a, ly=ly: tn(dx1, a["o"], G(ly.attn.to_out.weight), T, D, D))
@@ -886,21 +1000,20 @@ class FusionEngine:
             if grouped:
                 gw2, gwo = G(ly.ff.feedforward[2].weight), G(ly.attn.to_out.weight)
                 extra = [extra_top] if (bi == 0 and extra_top is not None) else []
-                on_side(lambda dqkv=dqkv, dh=dh, dxo=dxo, dx1=dx1, a=a, gq=gq, gw1=gw1, gw2=gw2, gwo=gwo, extra=extra: self.gemm_tn_acc_group(
-                    [(dqkv, a["xn_b"], gq, 3 * D, D), (dh, a["x1n_b"], gw1, I, D), (dh[:, Ip:], a["x1n_b"], gw1[I:], I, D),
+                on_side(lambda dqkv=dqkv, dh=dh, dxo=dxo, dx1=dx1, a=a, gq=gq, gw1=gw1, gw2=gw2, gwo=gwo, extra=extra: self._tn_group(
+                    ws, [(dqkv, a["xn_b"], gq, 3 * D, D), (dh, a["x1n_b"], gw1, I, D), (dh[:, Ip:], a["x1n_b"], gw1[I:], I, D),
                      (dxo, a["g"], gw2, D, I), (dx1, a["o"], gwo, D, D)] + extra, T))
             else:
                 on_side(lambda dqkv=dqkv, a=a, gq=gq: tn(dqkv, a["xn_b"], gq, T, 3 * D, D))
             self.gemm_nt(dqkv, w["qkvT"], dx_other, T, D, 3 * D, residual=dx)          # d xn = dqkv @ Wqkv + d x1
-            self.ln_bwd(dx_other, D, ws["x"][i], g, a["m1"], a["r1"], T, D, G(g), dx=dx, dx_bf16=below)  # dx = d x_in
+            self._ln_bwd(ws, dx_other, D, ws["x"][i], g, a["m1"], a["r1"], T, D, G(g), dx=dx, dx_bf16=below)  # dx = d x_in
             on_side(lambda bi=bi: bucket_ready(bi + 1))
         # dx = gradient w.r.t. the packed encoder output (b, N, D)
         if self.eao:          # the gradients of a modality's replicas, summed into the segment its encoder wrote
             for src, dst, n in self.st.copies:
                 call("mca_rows_copy_add", dx.data_ptr() + dst * D * 4, N * D, dx.data_ptr() + src * D * 4, N * D, n, D, b, 1, stream_ptr())
         if self.F:
-            call("mca_reduce_rows", dx.data_ptr() + (N - self.F) * D * 4, D, N * D, self.F, ptr(G(m.fusion_tokens)), D,
-                 b * self.F, D, stream_ptr())
+            self._reduce_rows(ws, dx.data_ptr() + (N - self.F) * D * 4, D, N * D, self.F, ptr(G(m.fusion_tokens)), D, b * self.F, D)
         for mi, name in enumerate(m.modality_types):
             enc = m.encoders[name]
             n, off = self.st.token_dims[mi], self.offsets[mi]
@@ -909,12 +1022,12 @@ class FusionEngine:
                 e, te = ws["enc"][name], enc.token_encoder
                 kp = self.we[name]["kp"]
                 # (the Linear's bias gradient = column sums of this norm's dx: same launch)
-                self.ln_bwd(dx[off:], D, e["y"], te[2].weight, e["m2"], e["r2"], rows, D, G(te[2].weight), dbeta=G(te[2].bias),
+                self._ln_bwd(ws, dx[off:], D, e["y"], te[2].weight, e["m2"], e["r2"], rows, D, G(te[2].weight), dbeta=G(te[2].bias),
                             rowmask=e["mask"], dx=e["dy"], dx_bf16=e["dy_b"], y_bstride=N * D, period=n, dxsum=G(te[1].bias))
                 on_side(lambda e=e, te=te, rows=rows, enc=enc: tn(e["dy_b"], e["xin_b"], G(te[1].weight), rows, D, enc.input_size))
                 self.gemm_nt(e["dy_b"], self.we[name]["wT"], e["dxin"], rows, kp, D)
                 t2 = e["tokens"].view(rows, enc.input_size)
-                self.ln_bwd(e["dxin"], kp, t2, te[0].weight, e["m0"], e["r0"], rows, enc.input_size, G(te[0].weight),
+                self._ln_bwd(ws, e["dxin"], kp, t2, te[0].weight, e["m0"], e["r0"], rows, enc.input_size, G(te[0].weight),
                             dbeta=G(te[0].bias), rowmask=e["mask"])
             elif isinstance(enc, TabularEncoder):
                 self._backward_tabular(name, enc, ws, mi, dx)
@@ -936,14 +1049,19 @@ class FusionEngine:
         e, ve, G = ws["enc"][name], enc.value_encoder, self.grad_of
         gemb = G(enc.token_encoder.embedding.weight)
         # the table is added after the value path is masked: every row of dx reaches it; padding_idx row stays frozen
-        call("mca_reduce_rows", dx.data_ptr() + off * D * 4, D, N * D, n, ptr(gemb), D, rows, D, stream_ptr())
+        self._reduce_rows(ws, dx.data_ptr() + off * D * 4, D, N * D, n, ptr(gemb), D, rows, D)
         gemb[n - 1].zero_()
-        self.ln_bwd(dx[off:], D, e["y"], ve.norm.weight, e["m2"], e["r2"], rows, D, G(ve.norm.weight), dbeta=G(ve.norm.bias),
+        self._ln_bwd(ws, dx[off:], D, e["y"], ve.norm.weight, e["m2"], e["r2"], rows, D, G(ve.norm.weight), dbeta=G(ve.norm.bias),
                     rowmask=e["mask"], dx=e["dy"], dx_bf16=e["dy_b"], y_bstride=N * D, period=n, dxsum=G(ve.linear2.bias))
-        self._on_side(lambda: self.gemm_tn_acc(e["dy_b"], e["h1_b"], G(ve.linear2.weight), rows, D, D), 200 + mi, ws)
+        self._on_side(lambda: self._tn(ws, e["dy_b"], e["h1_b"], G(ve.linear2.weight), rows, D, D), 200 + mi, ws)
         self.gemm_nt(e["dy_b"], self.we[name]["w2T"], e["dh1"], rows, D, D)
-        call("mca_tab_value_bwd", ptr(e["dh1"]), D, ptr(e["h1_b"]), ptr(e["values"]), ptr(G(ve.linear1.weight)),
-             ptr(G(ve.linear1.bias)), rows, D, float(ve.max_value), stream_ptr())
+        if self._deterministic:
+            s = self._det_scratch(ws, hip.lib().mca_tab_value_bwd_det_scratch(rows, D))
+            call("mca_tab_value_bwd_det", ptr(e["dh1"]), D, ptr(e["h1_b"]), ptr(e["values"]), ptr(G(ve.linear1.weight)),
+                 ptr(G(ve.linear1.bias)), rows, D, float(ve.max_value), ptr(s), s.numel(), stream_ptr())
+        else:
+            call("mca_tab_value_bwd", ptr(e["dh1"]), D, ptr(e["h1_b"]), ptr(e["values"]), ptr(G(ve.linear1.weight)),
+                 ptr(G(ve.linear1.bias)), rows, D, float(ve.max_value), stream_ptr())
 
     # ------------------------------------------------------------------------------------------------
     # model-level forward (autograd node)

@@ -37,6 +37,10 @@ class GraphedStep:
         self.model, self.opt, self.clip, self.dp = model, optimizer, float(clip), dp
         eng = model.engine
         self.direct = eng.can_forward_backward()
+        # the capture holds the launches of the mode the engine is in now (deterministic or not): the engine refuses to change
+        # the mode while this object is alive (FusionEngine.set_deterministic)
+        self.deterministic = eng.deterministic
+        eng._captured.add(self)
         # weight-gradient GEMMs on the side stream: inside a graph the fork / join edges cost more than the overlap gains at
         # every size tried (one box, alternating processes: b = 32 21.9 ms with, 21.5 without; b = 8 7.90-8.02 with, 7.80 without)
         eng.overlap_wgrad = bool(overlap_wgrad)

@@ -148,6 +148,14 @@ class TnGroupPlan(C.Structure):
     _fields_ = [("grouped", C.c_int), ("launch", GemmPlan), ("part", TnPartition)]
 
 
+class TnDetPlan(C.Structure):
+    _fields_ = [("launch", GemmPlan), ("slots", C.c_int), ("slot_stride", C.c_int64), ("scratch_floats", C.c_int64)]
+
+
+class TnGroupDetPlan(C.Structure):
+    _fields_ = [("plan", TnGroupPlan), ("slots", C.c_int), ("slot_stride", C.c_int64), ("scratch_floats", C.c_int64)]
+
+
 PLAN_NT, PLAN_LNRES, PLAN_GEGLU_FWD, PLAN_GEGLU_BWD = range(4)          # `entry` of mca_dbg_plan_gemm_nt
 
 _P, _I64, _I, _F = C.c_void_p, C.c_int64, C.c_int, C.c_float
@@ -210,6 +218,17 @@ SIGNATURES = {
     "mca_probe_tn_workspace": (_I64, [_I64, _I64, _I64]),
     "mca_probe_tn_f32": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, _I64, _P, _P, _P]),
     "mca_probe_loss_accum": (_I, [_P, _I64, _I64, _P, _P]),
+    # deterministic forms: the plain form's arguments + (scratch, scratch_floats) before the stream, and their size queries
+    "mca_gemm_tn_acc_det_scratch": (_I64, [_I64, _I64, _I64]),
+    "mca_gemm_tn_acc_det": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P, _I64, _P]),
+    "mca_gemm_tn_acc_group_det_scratch": (_I64, [C.POINTER(_I64), C.POINTER(_I64), _I, _I64, _I]),
+    "mca_gemm_tn_acc_group_det": (_I, [_P, _I, _I64, _P, _I64, _P]),
+    "mca_layernorm_bwd_det_scratch": (_I64, [_I64, _I]),
+    "mca_layernorm_bwd_det": (_I, [_P, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I, _P, _I64, _P]),
+    "mca_reduce_rows_det_scratch": (_I64, [_I64, _I64, _I]),
+    "mca_reduce_rows_det": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I, _P, _I64, _P]),
+    "mca_tab_value_bwd_det_scratch": (_I64, [_I64, _I]),
+    "mca_tab_value_bwd_det": (_I, [_P, _I64, _P, _P, _P, _P, _I64, _I, _F, _P, _I64, _P]),
 }
 # measurement hooks (include/mca_hip_debug.h): exported by the library, not part of the drop-in ABI
 DEBUG_SIGNATURES = {
@@ -219,6 +238,8 @@ DEBUG_SIGNATURES = {
     "mca_dbg_plan_gemm_nt": (_I, [_I, C.POINTER(NtProblem), _I, C.POINTER(GemmPlan)]),
     "mca_dbg_plan_gemm_tn": (_I, [_I64, _I64, _I64, C.POINTER(GemmPlan)]),
     "mca_dbg_plan_gemm_tn_group": (_I, [C.POINTER(_I64), C.POINTER(_I64), _I, _I64, _I, C.POINTER(TnGroupPlan)]),
+    "mca_dbg_plan_gemm_tn_det": (_I, [_I64, _I64, _I64, C.POINTER(TnDetPlan)]),
+    "mca_dbg_plan_gemm_tn_group_det": (_I, [C.POINTER(_I64), C.POINTER(_I64), _I, _I64, _I, C.POINTER(TnGroupDetPlan)]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -347,7 +368,8 @@ def profile_stop():
 
 
 def call(name: str, *args, flops: float = 0.0):
-    if PROFILE is not None and _PROFILE_ON and name in PROFILE["names"]:
+    # (a deterministic form is timed wherever its plain form is asked for, under its own name)
+    if PROFILE is not None and _PROFILE_ON and (name in PROFILE["names"] or (name.endswith("_det") and name[:-4] in PROFILE["names"])):
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
         check(getattr(lib(), name)(*args), name)

@@ -182,6 +182,12 @@ def main():
     # --graph: the whole step replayed as one hipGraph, or under data parallelism as a chain of graph segments cut at the
     # collectives (graph.GraphedStep; batches have static shapes: the collators pad every modality to its pad_len)
     use_graph, graphed = "--graph" in sys.argv, None
+    # --deterministic: the fixed-order gradient sums ("Deterministic mode"): the same weights, optimizer state
+    # and batches give the same bits on every run; set before the first step, so a captured step is captured in that mode
+    if "--deterministic" in sys.argv:
+        model.engine.set_deterministic(True)
+        if rank == 0:
+            print("deterministic mode: on (fixed-order parameter-gradient sums)", flush=True)
     lr_at = lambda st: config.lr * lr_factor(config.lr_scheduler_type, st * sched_stride, config.num_warmup_steps, total_steps * sched_stride)
     model.train()
     for epoch in range(config.start_epoch, config.epochs):
