@@ -28,7 +28,7 @@ import torch
 
 from . import attention, hip
 from .attention import AttnGrads, AttnOperands, _OnePassSched, _Sched, _dev
-from .encoders import EmbeddedSequenceEncoder, TabularEncoder
+from .encoder_steps import step_for
 from .hip import AttnBwd1Args, AttnBwd2Args, AttnFp8BwdOperands, AttnFp8Operands, AttnFwdArgs, LossTerm, call, ptr, stream_ptr
 
 LN_EPS = 1e-5
@@ -57,6 +57,14 @@ def debug_options() -> dict:
             raise ValueError(f"MCA_DEBUG: unknown switch '{k}' (known: {sorted(opts)})")
         opts[k] = int(v) if k == "dkv_keys" else (v.strip() not in ("0", "", "false"))
     return opts
+
+
+def _ln_bwd_args(dy, ldy, x, gamma, mean, rstd, rows, cols, dgamma, dbeta=None, rowmask=None, dx=None, dx_bf16=None,
+                 y_bstride=0, period=0, dxsum=None):
+    """mca_layernorm_bwd's arguments up to the stream"""
+    return (ptr(dy), ldy, y_bstride, period, ptr(x), x.stride(0), ptr(gamma), ptr(mean), ptr(rstd),
+            ptr(rowmask), ptr(dx), dx.stride(0) if dx is not None else 0, ptr(dx_bf16),
+            dx_bf16.stride(0) if dx_bf16 is not None else 0, ptr(dgamma), ptr(dbeta), ptr(dxsum), rows, cols)
 
 
 class FusionEngine:
@@ -90,6 +98,8 @@ class FusionEngine:
         self.mask_mfma = int(self.st.kgroup.max()) <= 14 and self.dbg["mask_mfma"]
         self._flatten_parameters()
         self._build_static()
+        # one step object per modality (encoder_steps.py): everything that depends on the encoder's kind, its bf16 weight copies included
+        self.enc_steps = [step_for(self, name, mi, model.encoders[name]) for mi, name in enumerate(model.modality_types)]
         self._alloc_weights()
         self._ws: Dict[int, dict] = {}
         self._weights_version = -1
@@ -223,14 +233,6 @@ class FusionEngine:
             self.wl.append(dict(qkv=bf(3 * D, D), qkvT=bf(D, 3 * D), o=bf(D, D), oT=bf(D, D),
                                 w1=bf(2 * Ip, D), w1T=bf(D, 2 * Ip), w2=bf(D, Ip), w2T=bf(Ip, D)))
         self.wp = dict(q=bf(D, D), qT=bf(D, D), kv=bf(2 * D, D), kvT=bf(D, 2 * D), o=bf(D, D), oT=bf(D, D))
-        self.we = {}
-        for name in self.model.modality_types:
-            enc = self.model.encoders[name]
-            if isinstance(enc, EmbeddedSequenceEncoder):
-                kp = _pad_to(enc.input_size, 64)
-                self.we[name] = dict(kp=kp, w=bf(D, kp), wT=bf(kp, D))
-            elif isinstance(enc, TabularEncoder):
-                self.we[name] = dict(w2=bf(D, D), w2T=bf(D, D))
 
     def _cast(self, src: torch.Tensor, dst: torch.Tensor, transpose=False, dst_row0=0, dst_col0=0, scale=0.0):
         """dst[dst_row0:, dst_col0:] (bf16) <- src (fp32 2-D), zero padding untouched (buffers start zeroed).  Only
@@ -366,14 +368,8 @@ class FusionEngine:
             self._cast(ap.to_q.weight.data, self.wp["q"], scale=self.q_scale); self._cast(ap.to_q.weight.data, self.wp["qT"], transpose=True)
             self._cast(ap.to_kv.weight.data, self.wp["kv"]); self._cast(ap.to_kv.weight.data, self.wp["kvT"], transpose=True)
             self._cast(ap.to_out.weight.data, self.wp["o"]); self._cast(ap.to_out.weight.data, self.wp["oT"], transpose=True)
-        for name in m.modality_types:
-            enc = m.encoders[name]
-            if isinstance(enc, EmbeddedSequenceEncoder):
-                self._cast(enc.token_encoder[1].weight.data, self.we[name]["w"])
-                self._cast(enc.token_encoder[1].weight.data, self.we[name]["wT"], transpose=True)
-            elif isinstance(enc, TabularEncoder):
-                self._cast(enc.value_encoder.linear2.weight.data, self.we[name]["w2"])
-                self._cast(enc.value_encoder.linear2.weight.data, self.we[name]["w2T"], transpose=True)
+        for s in self.enc_steps:
+            s.casts()
         arr = (hip.CastDesc * len(self._cast_list))(*self._cast_list)
         self._cast_n = len(self._cast_list)
         self._cast_table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
@@ -427,18 +423,7 @@ class FusionEngine:
             # (+ 64 rows: the kernel reads whole 64-row tiles, the last one past its rows)
             ws["q_hm"] = torch.zeros((b * H * N + 64) * 64, dtype=torch.bfloat16, device=dev)
             ws["do_hm"] = torch.zeros((b * H * N + 64) * 64, dtype=torch.bfloat16, device=dev)
-        ws["enc"] = {}
-        for mi, name in enumerate(self.model.modality_types):
-            enc = self.model.encoders[name]
-            n = self.st.token_dims[mi]
-            rows = b * n
-            if isinstance(enc, EmbeddedSequenceEncoder):
-                kp = self.we[name]["kp"]
-                ws["enc"][name] = dict(xin_b=bf(rows, kp), m0=f32(rows), r0=f32(rows), y=f32(rows, D), m2=f32(rows), r2=f32(rows),
-                                       dy=f32(rows, D), dy_b=bf(rows, D), dxin=f32(rows, kp), mask=u8(rows))
-            elif isinstance(enc, TabularEncoder):
-                ws["enc"][name] = dict(h1_b=bf(rows, D), y=f32(rows, D), m2=f32(rows), r2=f32(rows), dy=f32(rows, D),
-                                       dy_b=bf(rows, D), dh1=f32(rows, D), mask=u8(rows))
+        ws["enc"] = {s.name: s.workspace(b, f32, bf, u8) for s in self.enc_steps}
         ws["side"], ws["side_events"] = torch.cuda.Stream(device=dev), []          # side stream of the weight-gradient GEMMs
         if self._deterministic:
             self._alloc_det_scratch(ws)
@@ -450,24 +435,22 @@ class FusionEngine:
     # ------------------------------------------------------------------------------------------------
     def _det_need(self, b: int) -> int:
         """floats of scratch the largest deterministic launch of a b-sample backward needs: the library's size queries over
-        every call site of _backward_part, _backward_layers_and_encoders and _backward_tabular (grouped AND single forms of
-        the weight gradients, so the figure holds whatever group_wgrad says)"""
+        every call site of _backward_part and _backward_layers_and_encoders (grouped AND single forms of the weight gradients,
+        so the figure holds whatever group_wgrad says) and over every encoder step's det_shapes()"""
         L, D, I, R, F, N, T = hip.lib(), self.D, self.I, self.R, self.F, self.N, b * self.N
-        tn = [(b * R, D, D), (R, D, D), (T, 2 * D, D), (T, D, I), (T, I, D), (T, D, D), (T, 3 * D, D)]
-        ln, rr, tab = [(T, D)], [(b * R, R), (R, R)] + ([(b * F, F)] if F else []), []
-        for mi, name in enumerate(self.model.modality_types):
-            enc, rows = self.model.encoders[name], b * self.st.token_dims[mi]
-            if isinstance(enc, EmbeddedSequenceEncoder):
-                tn.append((rows, D, enc.input_size)); ln += [(rows, D), (rows, enc.input_size)]
-            elif isinstance(enc, TabularEncoder):
-                tn.append((rows, D, D)); ln.append((rows, D)); rr.append((rows, self.st.token_dims[mi])); tab.append(rows)
-        need = max(L.mca_gemm_tn_acc_det_scratch(*t) for t in tn)
+        shapes = dict(tn=[(b * R, D, D), (R, D, D), (T, 2 * D, D), (T, D, I), (T, I, D), (T, D, D), (T, 3 * D, D)],
+                      ln=[(T, D)], rr=[(b * R, R), (R, R)] + ([(b * F, F)] if F else []), tab=[])
+        for s in self.enc_steps:
+            for kind, more in s.det_shapes(b).items():
+                shapes[kind] += more
+        need = max(L.mca_gemm_tn_acc_det_scratch(*t) for t in shapes["tn"])
         members = [(3 * D, D), (I, D), (I, D), (D, I), (D, D)]
         for ms in (members, members + [(2 * D, D)]):
             Ns, Ks = (C.c_int64 * len(ms))(*[m[0] for m in ms]), (C.c_int64 * len(ms))(*[m[1] for m in ms])
             need = max(need, L.mca_gemm_tn_acc_group_det_scratch(Ns, Ks, len(ms), T, 0))
-        need = max([need] + [L.mca_layernorm_bwd_det_scratch(r, c) for r, c in ln] + [L.mca_reduce_rows_det_scratch(r, p, D) for r, p in rr]
-                   + [L.mca_tab_value_bwd_det_scratch(r, D) for r in tab])
+        need = max([need] + [L.mca_layernorm_bwd_det_scratch(r, c) for r, c in shapes["ln"]]
+                   + [L.mca_reduce_rows_det_scratch(r, p, D) for r, p in shapes["rr"]]
+                   + [L.mca_tab_value_bwd_det_scratch(r, D) for r in shapes["tab"]])
         return int(need)
 
     def _alloc_det_scratch(self, ws):
@@ -483,42 +466,41 @@ class FusionEngine:
         assert need <= reg.numel(), f"deterministic scratch: a launch needs {need} floats, the workspace holds {reg.numel()}"
         return reg
 
-    def _tn(self, ws, A, B, Cgrad, R, N, K):
-        """gemm_tn_acc, or its fixed-order form in deterministic mode"""
+    def _sum_launch(self, ws, name, args, scratch_query, flops=0.0):
+        """The one launcher of the five entry points whose result depends on the order of a sum (mca_gemm_tn_acc,
+        mca_gemm_tn_acc_group, mca_layernorm_bwd, mca_reduce_rows, mca_tab_value_bwd).  args: the plain form's arguments up to
+        the stream.  Deterministic mode launches <name>_det: the same arguments + (scratch, scratch_floats) before the stream
+        (hip.py), the scratch sized by <name>_det_scratch(*scratch_query()): the query's arguments are built in that mode only."""
         if not self._deterministic:
-            return self.gemm_tn_acc(A, B, Cgrad, R, N, K)
-        s = self._det_scratch(ws, hip.lib().mca_gemm_tn_acc_det_scratch(R, N, K))
-        call("mca_gemm_tn_acc_det", ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(Cgrad), Cgrad.stride(0), R, N, K, ptr(s), s.numel(),
-             stream_ptr(), flops=2.0 * R * N * K)
+            return call(name, *args, stream_ptr(), flops=flops)
+        s = self._det_scratch(ws, getattr(hip.lib(), name + "_det_scratch")(*scratch_query()))
+        call(name + "_det", *args, ptr(s), s.numel(), stream_ptr(), flops=flops)
+
+    def _tn(self, ws, A, B, Cgrad, R, N, K):
+        """Cgrad[N,K] += A[R,N]^T B[R,K]"""
+        self._sum_launch(ws, "mca_gemm_tn_acc", (ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(Cgrad), Cgrad.stride(0), R, N, K),
+                         lambda: (R, N, K), flops=2.0 * R * N * K)
 
     def _tn_group(self, ws, members, R):
-        if not self._deterministic:
-            return self.gemm_tn_acc_group(members, R)
-        arr = (hip.TnDesc * len(members))()
+        """members: [(A, B, Cgrad, N, K)]: Cgrad[N,K] += A[R,N]^T B[R,K] for every member, one launch (mca_gemm_tn_acc_group)"""
+        n = len(members)
+        arr = (hip.TnDesc * n)()
         fl = 0.0
         for d, (A, B, Cg, N, K) in zip(arr, members):
             d.A, d.lda, d.B, d.ldb, d.C, d.ldc, d.N, d.K = ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(Cg), Cg.stride(0), N, K
             fl += 2.0 * R * N * K
-        Ns, Ks = (C.c_int64 * len(members))(*[m[3] for m in members]), (C.c_int64 * len(members))(*[m[4] for m in members])
-        s = self._det_scratch(ws, hip.lib().mca_gemm_tn_acc_group_det_scratch(Ns, Ks, len(members), R, 0))
-        call("mca_gemm_tn_acc_group_det", C.byref(arr), len(members), R, ptr(s), s.numel(), stream_ptr(), flops=fl)
+        i64s = lambda k: (C.c_int64 * n)(*[m[k] for m in members])
+        self._sum_launch(ws, "mca_gemm_tn_acc_group", (C.byref(arr), n, R), lambda: (i64s(3), i64s(4), n, R, 0), flops=fl)
 
-    def _ln_bwd(self, ws, dy, ldy, x, gamma, mean, rstd, rows, cols, dgamma, dbeta=None, rowmask=None, dx=None, dx_bf16=None,
-                y_bstride=0, period=0, dxsum=None):
-        if not self._deterministic:
-            return self.ln_bwd(dy, ldy, x, gamma, mean, rstd, rows, cols, dgamma, dbeta=dbeta, rowmask=rowmask, dx=dx, dx_bf16=dx_bf16,
-                               y_bstride=y_bstride, period=period, dxsum=dxsum)
-        s = self._det_scratch(ws, hip.lib().mca_layernorm_bwd_det_scratch(rows, cols))
-        call("mca_layernorm_bwd_det", ptr(dy), ldy, y_bstride, period, ptr(x), x.stride(0), ptr(gamma), ptr(mean), ptr(rstd),
-             ptr(rowmask), ptr(dx), dx.stride(0) if dx is not None else 0, ptr(dx_bf16),
-             dx_bf16.stride(0) if dx_bf16 is not None else 0, ptr(dgamma), ptr(dbeta), ptr(dxsum), rows, cols, ptr(s), s.numel(), stream_ptr())
+    def _ln_bwd(self, ws, dy, ldy, x, gamma, mean, rstd, rows, cols, dgamma, **optional):
+        """optional: dbeta, rowmask, dx, dx_bf16, y_bstride, period, dxsum (_ln_bwd_args)"""
+        self._sum_launch(ws, "mca_layernorm_bwd", _ln_bwd_args(dy, ldy, x, gamma, mean, rstd, rows, cols, dgamma, **optional),
+                         lambda: (rows, cols))
 
     def _reduce_rows(self, ws, src, lds, src_bstride, period, dst, ldd, rows, cols):
         """src, dst: device addresses"""
-        if not self._deterministic:
-            return call("mca_reduce_rows", src, lds, src_bstride, period, dst, ldd, rows, cols, stream_ptr())
-        s = self._det_scratch(ws, hip.lib().mca_reduce_rows_det_scratch(rows, period, cols))
-        call("mca_reduce_rows_det", src, lds, src_bstride, period, dst, ldd, rows, cols, ptr(s), s.numel(), stream_ptr())
+        self._sum_launch(ws, "mca_reduce_rows", (src, lds, src_bstride, period, dst, ldd, rows, cols),
+                         lambda: (rows, period, cols))
 
     # ------------------------------------------------------------------------------------------------
     # thin kernel wrappers
@@ -535,22 +517,6 @@ class FusionEngine:
             hip.set_tag("")
 
     @staticmethod
-    def gemm_tn_acc(A, B, Cgrad, R, N, K):
-        """Cgrad[N,K] += A[R,N]^T B[R,K]"""
-        call("mca_gemm_tn_acc", ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(Cgrad), Cgrad.stride(0), R, N, K, stream_ptr(),
-             flops=2.0 * R * N * K)
-
-    @staticmethod
-    def gemm_tn_acc_group(members, R):
-        """members: [(A, B, Cgrad, N, K)]: Cgrad[N,K] += A[R,N]^T B[R,K] for every member, one launch (mca_gemm_tn_acc_group)"""
-        arr = (hip.TnDesc * len(members))()
-        fl = 0.0
-        for d, (A, B, Cg, N, K) in zip(arr, members):
-            d.A, d.lda, d.B, d.ldb, d.C, d.ldc, d.N, d.K = ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(Cg), Cg.stride(0), N, K
-            fl += 2.0 * R * N * K
-        call("mca_gemm_tn_acc_group", C.byref(arr), len(members), R, stream_ptr(), flops=fl)
-
-    @staticmethod
     def ln_fwd(x, gamma, rows, cols, mean, rstd, beta=None, rowmask=None, add=None, period=0, y=None, ldy=0, y_bstride=0,
                y_bf16=None, cols_pad=0):
         call("mca_layernorm_fwd", ptr(x), x.stride(0), ptr(gamma), ptr(beta), ptr(rowmask), ptr(add), period,
@@ -558,11 +524,10 @@ class FusionEngine:
              ptr(mean), ptr(rstd), rows, cols, LN_EPS, stream_ptr())
 
     @staticmethod
-    def ln_bwd(dy, ldy, x, gamma, mean, rstd, rows, cols, dgamma, dbeta=None, rowmask=None, dx=None, dx_bf16=None,
-               y_bstride=0, period=0, dxsum=None):
-        call("mca_layernorm_bwd", ptr(dy), ldy, y_bstride, period, ptr(x), x.stride(0), ptr(gamma), ptr(mean), ptr(rstd),
-             ptr(rowmask), ptr(dx), dx.stride(0) if dx is not None else 0, ptr(dx_bf16),
-             dx_bf16.stride(0) if dx_bf16 is not None else 0, ptr(dgamma), ptr(dbeta), ptr(dxsum), rows, cols, stream_ptr())
+    def ln_bwd(*args, **optional):
+        """the plain launch with _ln_bwd_args' parameters, callable without an engine (tools/bench_ln.py); the engine's own launches
+        go through _ln_bwd"""
+        call("mca_layernorm_bwd", *_ln_bwd_args(*args, **optional), stream_ptr())
 
     def layer_attention(self, ws, i):
         """-> (AttnOperands, AttnGrads) of fusion layer i: q | k | v and dq | dk | dv are the column blocks of the packed (T, 3D)
@@ -675,7 +640,7 @@ class FusionEngine:
     # ------------------------------------------------------------------------------------------------
     # forward
     # ------------------------------------------------------------------------------------------------
-    def _encode(self, batch, ws, need_grad: bool, renorm: bool = True):
+    def _encode(self, batch, ws, need_grad: bool):
         """encoders + packing (model.py:455-466): writes ws['x'][0] (b, N, D), ws['padding'] (b, N) and ws['present'] (b,)
         int32 (bit i = modality i has a valid token in that sample); returns modality_sample_mask {name: (b,) bool}."""
         m, D, N, b = self.model, self.D, self.N, ws["b"]
@@ -685,11 +650,10 @@ class FusionEngine:
         pk = hip.PackMasksArgs()
         keep = []                         # keeps converted mask tensors alive until the launch is enqueued
         native_idx = []
-        for mi, name in enumerate(m.modality_types):
-            enc = m.encoders[name]
-            if not isinstance(enc, (EmbeddedSequenceEncoder, TabularEncoder)):
+        for step in self.enc_steps:
+            if not step.native:
                 continue
-            n, off = self.st.token_dims[mi], self.offsets[mi]
+            name, mi, n, off = step.name, step.mi, step.n, step.off
             am = batch[name]["attention_mask"]
             if am.dtype == torch.bool or am.dtype == torch.uint8:
                 eb = 1
@@ -704,7 +668,7 @@ class FusionEngine:
             keep.append(am)
             d = pk.m[len(native_idx)]
             d.mask, d.elem_bytes, d.n, d.offset = am.data_ptr(), eb, n, off
-            d.rowmask = ws["enc"][name]["mask"].data_ptr() if isinstance(enc, EmbeddedSequenceEncoder) else None
+            d.rowmask = step.row_mask(ws)
             native_idx.append(mi)
         foreign = len(native_idx) != len(m.modality_types)
         if native_idx:
@@ -717,37 +681,8 @@ class FusionEngine:
             present.zero_()
             for k, mi in enumerate(native_idx):
                 present |= ((ws["present_native"] >> k) & 1) << mi
-        for mi, name in enumerate(m.modality_types):
-            enc = m.encoders[name]
-            n, off = self.st.token_dims[mi], self.offsets[mi]
-            bm = batch[name]
-            if isinstance(enc, EmbeddedSequenceEncoder):
-                e = ws["enc"][name]
-                toks = bm["tokens"]
-                if toks.dtype != torch.float32 or not toks.is_contiguous():
-                    toks = toks.float().contiguous()
-                if toks.shape != (b, n, enc.input_size):
-                    raise AssertionError(f"{name}: tokens {tuple(toks.shape)} != {(b, n, enc.input_size)}")
-                e["tokens"] = toks
-                te = enc.token_encoder
-                rows = b * n
-                t2 = toks.view(rows, enc.input_size)
-                self.ln_fwd(t2, te[0].weight, rows, enc.input_size, e["m0"], e["r0"], beta=te[0].bias, rowmask=e["mask"],
-                            y_bf16=e["xin_b"], cols_pad=self.we[name]["kp"])
-                self.gemm_nt(e["xin_b"], self.we[name]["w"], e["y"], rows, D, self.we[name]["kp"], bias=te[1].bias)
-                pe = enc.positional_encoder.pe
-                self.ln_fwd(e["y"], te[2].weight, rows, D, e["m2"], e["r2"], beta=te[2].bias, rowmask=e["mask"], add=pe,
-                            period=n, y=x0[off:], ldy=D, y_bstride=N * D)
-            elif isinstance(enc, TabularEncoder):
-                self._encode_tabular(name, enc, bm, ws, mi, renorm)
-            else:
-                # user-registered torch encoder: run it with autograd and feed its tokens to the native trunk
-                with torch.enable_grad() if need_grad else torch.no_grad():
-                    toks, amask = enc(bm)
-                ws["foreign"][name] = toks
-                x0.view(b, N, D)[:, off:off + n].copy_(toks.detach().float())
-                ws["padding"].view(b, N)[:, off:off + n].copy_(amask.to(torch.bool))
-                present |= ((amask == 0).sum(dim=1) != 0).to(torch.int32) << mi
+        for step in self.enc_steps:
+            step.forward(batch[step.name], ws, need_grad)
         if self.F:
             call("mca_bcast_rows", ptr(m.fusion_tokens.data), D, x0.data_ptr() + (N - self.F) * D * 4, D, N * D, self.F,
                  b * self.F, D, stream_ptr())
@@ -762,32 +697,6 @@ class FusionEngine:
         ws["present_cur"] = present
         bits = ((present[:, None] >> self._mod_shifts) & 1).to(torch.bool)          # (b, M): one small op for every modality
         return {name: bits[:, mi] for mi, name in enumerate(m.modality_types)}
-
-    def _renorm_table(self, enc, n):
-        emb = enc.token_encoder.embedding.weight
-        call("mca_embedding_renorm", ptr(emb.data), n, self.D, float(enc.token_encoder.max_norm), stream_ptr())
-
-    def _encode_tabular(self, name, enc, bm, ws, mi, renorm=True):
-        """encoders.py:90-96: E[t] (max_norm-renormalised in place) + LN(Linear2(ReLU(Linear1(min(x, max)))))), the value
-        part zeroed where x == padding_idx (-1).  The trunk's key-padding mask is the collator's attention_mask."""
-        D, N, b = self.D, self.N, ws["b"]
-        n, off = self.st.token_dims[mi], self.offsets[mi]
-        rows = b * n
-        e, ve = ws["enc"][name], enc.value_encoder
-        vals = bm["values"]
-        if vals.dtype != torch.float32 or not vals.is_contiguous():
-            vals = vals.float().contiguous()
-        if vals.shape != (b, n):
-            raise AssertionError(f"{vals.shape[1]} - {n}")                  # encoders.py:93
-        e["values"] = vals
-        emb = enc.token_encoder.embedding.weight
-        if renorm:
-            self._renorm_table(enc, n)
-        call("mca_tab_value_fwd", ptr(vals), ptr(ve.linear1.weight.data), ptr(ve.linear1.bias.data), ptr(e["h1_b"]), ptr(e["mask"]),
-             rows, D, float(ve.max_value), float(ve.padding_value), stream_ptr())
-        self.gemm_nt(e["h1_b"], self.we[name]["w2"], e["y"], rows, D, D, bias=ve.linear2.bias)
-        self.ln_fwd(e["y"], ve.norm.weight, rows, D, e["m2"], e["r2"], beta=ve.norm.bias, rowmask=e["mask"], add=emb.data,
-                    period=n, y=ws["x"][0][off:], ldy=D, y_bstride=N * D)
 
     def forward_trunk(self, ws):
         """fusion layers + final norm + attentive pooling -> ws['pooled'] (b*R, D)."""
@@ -1014,54 +923,9 @@ class FusionEngine:
                 call("mca_rows_copy_add", dx.data_ptr() + dst * D * 4, N * D, dx.data_ptr() + src * D * 4, N * D, n, D, b, 1, stream_ptr())
         if self.F:
             self._reduce_rows(ws, dx.data_ptr() + (N - self.F) * D * 4, D, N * D, self.F, ptr(G(m.fusion_tokens)), D, b * self.F, D)
-        for mi, name in enumerate(m.modality_types):
-            enc = m.encoders[name]
-            n, off = self.st.token_dims[mi], self.offsets[mi]
-            rows = b * n
-            if isinstance(enc, EmbeddedSequenceEncoder):
-                e, te = ws["enc"][name], enc.token_encoder
-                kp = self.we[name]["kp"]
-                # (the Linear's bias gradient = column sums of this norm's dx: same launch)
-                self._ln_bwd(ws, dx[off:], D, e["y"], te[2].weight, e["m2"], e["r2"], rows, D, G(te[2].weight), dbeta=G(te[2].bias),
-                            rowmask=e["mask"], dx=e["dy"], dx_bf16=e["dy_b"], y_bstride=N * D, period=n, dxsum=G(te[1].bias))
-                on_side(lambda e=e, te=te, rows=rows, enc=enc: tn(e["dy_b"], e["xin_b"], G(te[1].weight), rows, D, enc.input_size))
-                self.gemm_nt(e["dy_b"], self.we[name]["wT"], e["dxin"], rows, kp, D)
-                t2 = e["tokens"].view(rows, enc.input_size)
-                self._ln_bwd(ws, e["dxin"], kp, t2, te[0].weight, e["m0"], e["r0"], rows, enc.input_size, G(te[0].weight),
-                            dbeta=G(te[0].bias), rowmask=e["mask"])
-            elif isinstance(enc, TabularEncoder):
-                self._backward_tabular(name, enc, ws, mi, dx)
-            else:
-                toks = ws["foreign"][name]
-                if toks.requires_grad:
-                    # the foreign encoder's parameters live in the flat buffers too: point their .grad at the flat views so
-                    # that autograd ACCUMULATES in place (FusedAdamW.zero_grad leaves None, and a fresh .grad tensor would be
-                    # replaced by the zeroed flat view after this backward)
-                    for p in enc.parameters():
-                        p.grad = G(p)
-                    torch.autograd.backward(toks, dx.view(b, N, D)[:, off:off + n].to(toks.dtype))
+        for step in self.enc_steps:
+            step.backward(ws, dx, on_side)
         on_side(lambda: bucket_ready(len(self.bucket_bounds) - 1))
-
-    def _backward_tabular(self, name, enc, ws, mi, dx):
-        D, N, b = self.D, self.N, ws["b"]
-        n, off = self.st.token_dims[mi], self.offsets[mi]
-        rows = b * n
-        e, ve, G = ws["enc"][name], enc.value_encoder, self.grad_of
-        gemb = G(enc.token_encoder.embedding.weight)
-        # the table is added after the value path is masked: every row of dx reaches it; padding_idx row stays frozen
-        self._reduce_rows(ws, dx.data_ptr() + off * D * 4, D, N * D, n, ptr(gemb), D, rows, D)
-        gemb[n - 1].zero_()
-        self._ln_bwd(ws, dx[off:], D, e["y"], ve.norm.weight, e["m2"], e["r2"], rows, D, G(ve.norm.weight), dbeta=G(ve.norm.bias),
-                    rowmask=e["mask"], dx=e["dy"], dx_bf16=e["dy_b"], y_bstride=N * D, period=n, dxsum=G(ve.linear2.bias))
-        self._on_side(lambda: self._tn(ws, e["dy_b"], e["h1_b"], G(ve.linear2.weight), rows, D, D), 200 + mi, ws)
-        self.gemm_nt(e["dy_b"], self.we[name]["w2T"], e["dh1"], rows, D, D)
-        if self._deterministic:
-            s = self._det_scratch(ws, hip.lib().mca_tab_value_bwd_det_scratch(rows, D))
-            call("mca_tab_value_bwd_det", ptr(e["dh1"]), D, ptr(e["h1_b"]), ptr(e["values"]), ptr(G(ve.linear1.weight)),
-                 ptr(G(ve.linear1.bias)), rows, D, float(ve.max_value), ptr(s), s.numel(), stream_ptr())
-        else:
-            call("mca_tab_value_bwd", ptr(e["dh1"]), D, ptr(e["h1_b"]), ptr(e["values"]), ptr(G(ve.linear1.weight)),
-                 ptr(G(ve.linear1.bias)), rows, D, float(ve.max_value), stream_ptr())
 
     # ------------------------------------------------------------------------------------------------
     # model-level forward (autograd node)
@@ -1071,8 +935,7 @@ class FusionEngine:
             return self._model_forward(batch, no_loss)
 
     def can_forward_backward(self) -> bool:
-        m = self.model
-        return all(isinstance(m.encoders[n], (EmbeddedSequenceEncoder, TabularEncoder)) for n in m.modality_types)
+        return all(s.native for s in self.enc_steps)
 
     def forward_backward(self, batch):
         """forward + loss + backward WITHOUT autograd: the same kernels as ``model(batch)`` followed by ``loss.backward()``, issued
