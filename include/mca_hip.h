@@ -150,6 +150,27 @@ int mca_tab_value_bwd(const float* dh1, int64_t ld, const uint16_t* h1, const fl
                       int64_t rows, int cols, float max_value, mca_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Token tables (encoders.py:17-37 as SequenceEncoder :145-166 and SparseTabularEncoder :100-120 use them): rows looked up
+ * by index.  idx: `rows` integers of idx_bytes = 8 or 4 each.  An index outside [0, vocab) is never dereferenced.
+ * --------------------------------------------------------------------------------------------- */
+/* For i < rows:  dst[(i/period)*dst_bstride + (i%period)*ldd + c]  =  (accumulate ? its old value : 0) + (table[idx[i]][c] +
+ * add[(i%period)*cols + c])   (add may be NULL; cols % 4 == 0, 16-byte aligned pointers and strides, else MCA_E_ALIGN).
+ * Before any row is read, the rows that occur in idx, and only those, are renormalised in place as nn.Embedding(max_norm)
+ * does on every forward: a row with L2 norm > max_norm is multiplied by max_norm / (norm + 1e-7), once however many tokens name
+ * it; every other row keeps its bits.  Three launches on the stream: mark, renormalise the marked rows, gather.
+ * marker: vocab int32 words owned by the caller, all zero on entry, all zero again when the call's launches have run (the
+ * kernels clear what they set: no memset).  An index out of range contributes no table row (the output row is the add part
+ * alone) and ORs oob_bit into *flag (flag may be NULL), the word of the finite check below.                              */
+int mca_embedding_lookup(float* table, int64_t vocab, int cols, float max_norm, const void* idx, int idx_bytes,
+                         int64_t rows, int64_t period, const float* add, float* dst, int64_t ldd, int64_t dst_bstride,
+                         int accumulate, int32_t* marker, int32_t* flag, int oob_bit, mca_stream_t stream);
+/* dtable[idx[i]][c] += dy[(i/period)*y_bstride + (i%period)*ldy + c] for every i < rows whose index is in range and is not
+ * padding_idx (negative: counted from the end, as nn.Embedding does; vocab: no padding row).  fp32 atomics, one wavefront
+ * instruction per 256 contiguous bytes of one table row; dtable is packed (vocab, cols).                                 */
+int mca_embedding_scatter_add(const float* dy, int64_t ldy, int64_t y_bstride, int64_t period, const void* idx, int idx_bytes,
+                              int64_t rows, float* dtable, int64_t vocab, int cols, int64_t padding_idx, mca_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Block-masked fused attention (model.py:73-105 as used by MCALayer :119 and attn_pool :472-473)
  * --------------------------------------------------------------------------------------------- */
 /* Packing of the per-modality attention masks (model.py:455-466; encoders.py:196-214 for the row masks): ONE launch
@@ -472,7 +493,7 @@ int mca_probe_tn_f32(const float* a, int64_t lda, const float* b, int64_t ldb, c
 int mca_probe_loss_accum(const float* loss_part, int64_t n, int64_t count, float* acc, mca_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Deterministic mode: fixed-order forms of the five entry points whose parameter gradients are sums of
+ * Deterministic mode: fixed-order forms of the six entry points whose parameter gradients are sums of
  * fp32 atomics ("Deterministic mode").  Each takes the arguments of its plain form plus
  * `scratch` (device, fp32) and its size in floats; the *_scratch queries (host only, nothing launched)
  * give the floats a problem needs.  A scratch that is NULL or too small: MCA_E_BADARG, nothing launched.
@@ -498,6 +519,11 @@ int mca_probe_loss_accum(const float* loss_part, int64_t n, int64_t count, float
  *                              for (rows, cols), so it does not depend on which pointers are NULL.
  *   mca_reduce_rows_det        S = row slabs; slot = [period][cols], slot_stride = period*cols.
  *   mca_tab_value_bwd_det      S = row slabs; slot = [2][cols]: dw1, db1; slot_stride = 2*cols.
+ *   mca_embedding_scatter_add_det   no slots: the scratch holds two packed int32 arrays of `rows` words, the tokens sorted by
+ *                              (table row, position) and their table rows (tokens that contribute nothing last), every
+ *                              word written by the first launch.  The second launch computes, per touched element,
+ *                              dtable = dtable + (((g_0 + g_1) + g_2) + ...), the row's tokens in position order: an
+ *                              order that depends on the index values and the shapes only.  rows, vocab < 2^31.
  * (S and the partition for a weight gradient: mca_dbg_plan_gemm_tn_det / _group_det, mca_hip_debug.h.)
  * cus: CU count to plan the grouped form for, 0 = the current device's.
  * --------------------------------------------------------------------------------------------- */
@@ -519,6 +545,10 @@ int mca_reduce_rows_det(const float* src, int64_t lds, int64_t src_bstride, int6
 int64_t mca_tab_value_bwd_det_scratch(int64_t rows, int cols);
 int mca_tab_value_bwd_det(const float* dh1, int64_t ld, const uint16_t* h1, const float* x, float* dw1, float* db1,
                           int64_t rows, int cols, float max_value, float* scratch, int64_t scratch_floats, mca_stream_t stream);
+int64_t mca_embedding_scatter_add_det_scratch(int64_t rows);
+int mca_embedding_scatter_add_det(const float* dy, int64_t ldy, int64_t y_bstride, int64_t period, const void* idx, int idx_bytes,
+                                  int64_t rows, float* dtable, int64_t vocab, int cols, int64_t padding_idx,
+                                  float* scratch, int64_t scratch_floats, mca_stream_t stream);
 
 #ifdef __cplusplus
 }

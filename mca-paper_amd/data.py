@@ -4,6 +4,10 @@
                      ``attention_mask (b, pad_len) bool`` True = pad; dropped modality = all-pad row.
   sequence / tabular: ``values (b, n) f32`` with -10000 for a dropped modality,
                      ``attention_mask (b, n) int64`` = (values == -10000).
+  token sequence:    ``tokens (b, n) int64`` uniform in [1, V), pad token 0 past the valid length,
+                     ``attention_mask (b, n) int64`` = (tokens == 0); dropped modality = all-pad row.
+  sparse tabular:    ``indices (b, n) int64`` as the token sequence's, ``data (b, n) f32`` in [1, 10), 0.0 where padded,
+                     ``attention_mask (b, n) int64`` = (indices == 0).
 """
 from __future__ import annotations
 
@@ -42,6 +46,21 @@ def synthetic_batch(model_config: dict, batch_size: int, seed: int = 1234, p_dro
             vals = torch.randn(batch_size, n, generator=g)
             vals = torch.where(drop[:, mi, None], torch.full_like(vals, -10000.0), vals)
             batch[name] = {"values": vals.to(device), "attention_mask": (vals == -10000).to(torch.long).to(device)}
+        elif c["type"] in ("SequenceEncoder", "SparseTabularEncoder"):
+            V = c.get("num_embeddings", 36602)
+            if lengths == "full":
+                ln = torch.full((batch_size,), n, dtype=torch.long)
+            else:
+                ln = torch.randint(1, n + 1, (batch_size,), generator=g)
+            ln = torch.where(drop[:, mi], torch.zeros_like(ln), ln)
+            pad = torch.arange(n)[None, :] >= ln[:, None]
+            idx = torch.randint(1, V, (batch_size, n), generator=g).masked_fill(pad, 0)
+            mask = (idx == 0).to(torch.long)
+            if c["type"] == "SequenceEncoder":
+                batch[name] = {"tokens": idx.to(device), "attention_mask": mask.to(device)}
+            else:
+                vals = (torch.rand(batch_size, n, generator=g) * 9.0 + 1.0).masked_fill(pad, 0.0)
+                batch[name] = {"indices": idx.to(device), "data": vals.to(device), "attention_mask": mask.to(device)}
         else:
             raise NotImplementedError(c["type"])
     return batch

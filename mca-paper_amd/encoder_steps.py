@@ -1,14 +1,17 @@
 """One step object per encoder kind: what FusionEngine needs from a modality's encoder - its bf16 weight copies and their cast records,
 its workspace buffers, the shapes of its deterministic launches, its forward and its backward.  The engine builds one per modality
 (step_for, the only place that looks at an encoder's type) and loops over them: a new encoder kind is a class here and a line in
-step_for.  Reference lines: encoders.py:196-214 (EmbeddedSequenceEncoder), :90-96 (TabularEncoder).
+step_for.  Reference lines: encoders.py:196-214 (EmbeddedSequenceEncoder), :90-96 (TabularEncoder), :161-166 (SequenceEncoder), :114-120
+(SparseTabularEncoder).
 This module binds its own `call` from .hip: a tool that records launches by rebinding `call` patches hip, engine AND this module."""
 from __future__ import annotations
 
 import torch
 
-from .encoders import EmbeddedSequenceEncoder, TabularEncoder
+from .encoders import EmbeddedSequenceEncoder, SequenceEncoder, SparseTabularEncoder, TabularEncoder
 from .hip import call, ptr, stream_ptr
+
+FLAG_INDEX_RANGE = 4          # the engine's flag word: bit 1 non-finite encoder input, bit 2 non-finite output, this one a token index outside its table
 
 
 class _Step:
@@ -76,9 +79,10 @@ class SequenceStep(_Step):
                     dbeta=G(te[0].bias), rowmask=e["mask"])
 
 
-class TabularStep(_Step):
-    """TabularEncoder: E[t] (max_norm-renormalised in place) + LN(Linear2(ReLU(Linear1(min(x, max))))), the value part zeroed where
-    x == padding_idx (-1).  The trunk's key-padding mask is the collator's attention_mask."""
+class _ValueChain(_Step):
+    """The ContinuousValueEncoder part that TabularStep and SparseTabularStep share: `mca_tab_value_fwd` (Linear(1, D) + ReLU on
+    min(x, max_value)) -> `mca_gemm_nt` + bias -> `mca_layernorm_fwd`, zero where x == padding_value, written into the packed token
+    matrix; and its backward.  The trunk's key-padding mask is the batch's attention_mask."""
     native = True
 
     def __init__(self, engine, name, mi, enc):
@@ -97,41 +101,146 @@ class TabularStep(_Step):
     def row_mask(self, ws):
         return None          # (its mask comes from the values: mca_tab_value_fwd)
 
-    def forward(self, bm, ws, need_grad):
-        eng, enc, n, D, b = self.eng, self.enc, self.n, self.D, ws["b"]
-        e, ve, rows = ws["enc"][self.name], enc.value_encoder, b * n
-        vals = bm["values"]
-        if vals.dtype != torch.float32 or not vals.is_contiguous():
-            vals = vals.float().contiguous()
-        if vals.shape != (b, n):
-            raise AssertionError(f"{vals.shape[1]} - {n}")                  # encoders.py:93
+    def _value_forward(self, vals, ws, add):
+        """vals (b, n) fp32 contiguous; add: (n, D) rows added after the mask, or None"""
+        eng, n, D = self.eng, self.n, self.D
+        e, ve, rows = ws["enc"][self.name], self.enc.value_encoder, ws["b"] * n
         e["values"] = vals
-        emb = enc.token_encoder.embedding.weight
-        call("mca_embedding_renorm", ptr(emb.data), n, D, float(enc.token_encoder.max_norm), stream_ptr())
         call("mca_tab_value_fwd", ptr(vals), ptr(ve.linear1.weight.data), ptr(ve.linear1.bias.data), ptr(e["h1_b"]), ptr(e["mask"]),
              rows, D, float(ve.max_value), float(ve.padding_value), stream_ptr())
         eng.gemm_nt(e["h1_b"], self.w2, e["y"], rows, D, D, bias=ve.linear2.bias)
-        eng.ln_fwd(e["y"], ve.norm.weight, rows, D, e["m2"], e["r2"], beta=ve.norm.bias, rowmask=e["mask"], add=emb.data,
+        eng.ln_fwd(e["y"], ve.norm.weight, rows, D, e["m2"], e["r2"], beta=ve.norm.bias, rowmask=e["mask"], add=add,
                    period=n, y=ws["x"][0][self.off:], ldy=D, y_bstride=self.N * D)
 
-    def det_shapes(self, b):
-        """the deterministic launches of backward(): the table's row sum, one LayerNorm backward, one weight gradient, Linear1"""
+    def _value_det_shapes(self, b):
+        """the deterministic launches of _value_backward(): one LayerNorm backward, one weight gradient, Linear1"""
         rows, D = b * self.n, self.D
-        return dict(rr=[(rows, self.n)], ln=[(rows, D)], tn=[(rows, D, D)], tab=[rows])
+        return dict(ln=[(rows, D)], tn=[(rows, D, D)], tab=[rows])
 
-    def backward(self, ws, dx, on_side):
+    def _value_backward(self, ws, dx, on_side):
         eng, n, off, D, N, G = self.eng, self.n, self.off, self.D, self.N, self.G
         e, ve, rows = ws["enc"][self.name], self.enc.value_encoder, ws["b"] * n
-        gemb = G(self.enc.token_encoder.embedding.weight)
-        # the table is added after the value path is masked: every row of dx reaches it; padding_idx row stays frozen
-        eng._reduce_rows(ws, dx.data_ptr() + off * D * 4, D, N * D, n, ptr(gemb), D, rows, D)
-        gemb[n - 1].zero_()
         eng._ln_bwd(ws, dx[off:], D, e["y"], ve.norm.weight, e["m2"], e["r2"], rows, D, G(ve.norm.weight), dbeta=G(ve.norm.bias),
                     rowmask=e["mask"], dx=e["dy"], dx_bf16=e["dy_b"], y_bstride=N * D, period=n, dxsum=G(ve.linear2.bias))
         on_side(lambda e=e, ve=ve, rows=rows: eng._tn(ws, e["dy_b"], e["h1_b"], G(ve.linear2.weight), rows, D, D))
         eng.gemm_nt(e["dy_b"], self.w2T, e["dh1"], rows, D, D)
         eng._sum_launch(ws, "mca_tab_value_bwd", (ptr(e["dh1"]), D, ptr(e["h1_b"]), ptr(e["values"]), ptr(G(ve.linear1.weight)),
                                                   ptr(G(ve.linear1.bias)), rows, D, float(ve.max_value)), lambda: (rows, D))
+
+
+class TabularStep(_ValueChain):
+    """TabularEncoder: E[t] (max_norm-renormalised in place) + LN(Linear2(ReLU(Linear1(min(x, max))))), the value part zeroed where
+    x == padding_idx (-1)."""
+
+    def forward(self, bm, ws, need_grad):
+        enc, n, D, b = self.enc, self.n, self.D, ws["b"]
+        vals = bm["values"]
+        if vals.dtype != torch.float32 or not vals.is_contiguous():
+            vals = vals.float().contiguous()
+        if vals.shape != (b, n):
+            raise AssertionError(f"{vals.shape[1]} - {n}")                  # encoders.py:93
+        emb = enc.token_encoder.embedding.weight
+        call("mca_embedding_renorm", ptr(emb.data), n, D, float(enc.token_encoder.max_norm), stream_ptr())
+        self._value_forward(vals, ws, emb.data)
+
+    def det_shapes(self, b):
+        """the deterministic launches of backward(): the table's row sum, then the value chain's"""
+        return dict(rr=[(b * self.n, self.n)], **self._value_det_shapes(b))
+
+    def backward(self, ws, dx, on_side):
+        eng, n, off, D, N, G = self.eng, self.n, self.off, self.D, self.N, self.G
+        gemb = G(self.enc.token_encoder.embedding.weight)
+        # the table is added after the value path is masked: every row of dx reaches it; padding_idx row stays frozen
+        eng._reduce_rows(ws, dx.data_ptr() + off * D * 4, D, N * D, n, ptr(gemb), D, ws["b"] * n, D)
+        gemb[n - 1].zero_()
+        self._value_backward(ws, dx, on_side)
+
+
+class _TableLookup:
+    """What the two indexed encoders share (mixed into a _Step): the table of `enc.token_encoder`, looked up by a (b, n) integer
+    tensor of the batch.  `mca_embedding_lookup` renormalises the rows the batch names and gathers them into the packed token
+    matrix; the table gradient is `mca_embedding_scatter_add` over the same indices.  An index outside the table sets
+    FLAG_INDEX_RANGE in the engine's flag word and contributes nothing, forward or backward."""
+
+    def _table_init(self):
+        te = self.enc.token_encoder
+        self.V, pad = te.num_embeddings, te.embedding.padding_idx
+        self.pad = self.V if pad is None else int(pad)          # (nn.Embedding has made a negative padding_idx positive)
+        self.marker = torch.zeros(self.V, dtype=torch.int32, device=self.eng.device)          # zero between launches (mca_hip.h)
+
+    def _indices(self, t, what, b):
+        # a floating-point index tensor is what SequenceCollator emits when a sample of the batch is missing (INTEGRATION.md)
+        if t.dtype not in (torch.int64, torch.int32):
+            t = t.to(torch.int64)
+        if not t.is_contiguous():
+            t = t.contiguous()
+        if t.shape != (b, self.n):
+            raise AssertionError(f"{self.name}: {what} {tuple(t.shape)} != {(b, self.n)}")
+        return t
+
+    def _lookup(self, idx, ws, add, accumulate):
+        eng, te, D = self.eng, self.enc.token_encoder, self.D
+        ws["enc"][self.name]["idx"] = idx
+        call("mca_embedding_lookup", ptr(te.embedding.weight.data), self.V, D, float(te.max_norm), ptr(idx), idx.element_size(),
+             ws["b"] * self.n, self.n, ptr(add), ws["x"][0].data_ptr() + self.off * D * 4, D, self.N * D, int(accumulate),
+             ptr(self.marker), ptr(eng.finite_flag) if eng.check_finite else None, FLAG_INDEX_RANGE, stream_ptr())
+
+    def _table_backward(self, ws, dx):
+        D, rows, idx = self.D, ws["b"] * self.n, ws["enc"][self.name]["idx"]
+        self.eng._sum_launch(ws, "mca_embedding_scatter_add",
+                             (dx.data_ptr() + self.off * D * 4, D, self.N * D, self.n, ptr(idx), idx.element_size(), rows,
+                              ptr(self.G(self.enc.token_encoder.embedding.weight)), self.V, D, self.pad), lambda: (rows,))
+
+
+class TokenSequenceStep(_Step, _TableLookup):
+    """SequenceEncoder: E[tokens] + positional table in one `mca_embedding_lookup`, straight into the packed token matrix; padded
+    positions are not zeroed (encoders.py:161-166).  The trunk's key-padding mask is the batch's attention_mask."""
+    native = True
+
+    def __init__(self, engine, name, mi, enc):
+        super().__init__(engine, name, mi, enc)
+        self._table_init()
+
+    def casts(self): pass
+    def workspace(self, b, f32, bf, u8): return {}
+    def row_mask(self, ws): return None
+
+    def forward(self, bm, ws, need_grad):
+        self._lookup(self._indices(bm["tokens"], "tokens", ws["b"]), ws, self.enc.positional_encoder.pe, False)
+
+    def det_shapes(self, b):
+        """the deterministic launch of backward(): the table gradient"""
+        return dict(emb=[b * self.n])
+
+    def backward(self, ws, dx, on_side):
+        self._table_backward(ws, dx)
+
+
+class SparseTabularStep(_ValueChain, _TableLookup):
+    """SparseTabularEncoder: the value chain of `data` written into the packed token matrix (zero where data == padding_idx), then
+    E[indices] added onto it, unmasked (encoders.py:114-120)."""
+
+    def __init__(self, engine, name, mi, enc):
+        super().__init__(engine, name, mi, enc)
+        self._table_init()
+
+    def forward(self, bm, ws, need_grad):
+        b = ws["b"]
+        idx, vals = self._indices(bm["indices"], "indices", b), bm["data"]
+        if vals.dtype != torch.float32 or not vals.is_contiguous():
+            vals = vals.float().contiguous()
+        if vals.shape != (b, self.n):
+            raise AssertionError(f"{self.name}: data {tuple(vals.shape)} != {(b, self.n)}")
+        self._value_forward(vals, ws, None)
+        self._lookup(idx, ws, None, True)
+
+    def det_shapes(self, b):
+        """the deterministic launches of backward(): the table gradient, then the value chain's"""
+        return dict(emb=[b * self.n], **self._value_det_shapes(b))
+
+    def backward(self, ws, dx, on_side):
+        self._table_backward(ws, dx)
+        self._value_backward(ws, dx, on_side)
 
 
 class ForeignStep(_Step):
@@ -169,4 +278,8 @@ def step_for(engine, name, mi, enc):
         return SequenceStep(engine, name, mi, enc)
     if isinstance(enc, TabularEncoder):
         return TabularStep(engine, name, mi, enc)
+    if isinstance(enc, SequenceEncoder):
+        return TokenSequenceStep(engine, name, mi, enc)
+    if isinstance(enc, SparseTabularEncoder):
+        return SparseTabularStep(engine, name, mi, enc)
     return ForeignStep(engine, name, mi, enc)

@@ -63,11 +63,13 @@ class EmbeddedSequenceEncoder(NativeEncoder):
 class _TokenTable(nn.Module):
     """``nn.Embedding(n, D, padding_idx, max_norm=1.0)`` as a parameter holder (encoders.py:17-37).  The
     max_norm renormalisation (rows with L2 norm > 1 rescaled in place on every forward) is done by the
-    engine before the table is used."""
+    engine before the table is used: of the whole table for TabularEncoder (every row is looked up), of the rows a
+    batch names for the indexed encoders."""
 
     def __init__(self, num_embeddings, embedding_dim, padding_idx=None, max_norm=1.0):
         super().__init__()
         self.max_norm = max_norm
+        self.num_embeddings = num_embeddings
         self.embedding = nn.Embedding(num_embeddings, embedding_dim, padding_idx=padding_idx)
 
 
@@ -96,9 +98,38 @@ class TabularEncoder(NativeEncoder):
         self.value_encoder = _ValueMLP(embedding_dim, dropout, max_value, padding_idx)
 
 
+class SequenceEncoder(NativeEncoder):
+    """Token ids: table row of ``batch["tokens"]`` (b, n) + positional table; padded positions are NOT zeroed, the mask is handed
+    through (encoders.py:145-166)."""
+    kind = "token_sequence"
+
+    def __init__(self, num_embeddings=36602, embedding_dim=512, padding_idx=0, dropout=0.0, max_tokens=1024, **kwargs):
+        super().__init__()
+        self.embedding_dim = embedding_dim
+        self.num_embeddings = num_embeddings
+        self.max_tokens = max_tokens
+        self.token_encoder = _TokenTable(num_embeddings, embedding_dim, padding_idx)
+        self.positional_encoder = PositionalEncoder(embedding_dim, dropout, max_tokens)
+
+
+class SparseTabularEncoder(NativeEncoder):
+    """Index / value lists: table row of ``batch["indices"]`` (b, n) + value MLP of ``batch["data"]`` (b, n), the value part zero
+    where data == padding_idx; no ``index`` buffer (encoders.py:100-120)."""
+    kind = "sparse_tabular"
+
+    def __init__(self, num_embeddings=36602, embedding_dim=512, padding_idx=0, dropout=0.0, max_value=10000, **kwargs):
+        super().__init__()
+        self.embedding_dim = embedding_dim
+        self.num_embeddings = num_embeddings
+        self.token_encoder = _TokenTable(num_embeddings, embedding_dim, padding_idx)
+        self.value_encoder = _ValueMLP(embedding_dim, dropout, max_value, padding_idx)
+
+
 encoders_dict: Dict[str, type] = {
     "EmbeddedSequenceEncoder": EmbeddedSequenceEncoder,
     "TabularEncoder": TabularEncoder,
+    "SequenceEncoder": SequenceEncoder,
+    "SparseTabularEncoder": SparseTabularEncoder,
 }
 
 

@@ -28,7 +28,7 @@ import torch
 
 from . import attention, hip
 from .attention import AttnGrads, AttnOperands, _OnePassSched, _Sched, _dev
-from .encoder_steps import step_for
+from .encoder_steps import FLAG_INDEX_RANGE, step_for
 from .hip import AttnBwd1Args, AttnBwd2Args, AttnFp8BwdOperands, AttnFp8Operands, AttnFwdArgs, LossTerm, call, ptr, stream_ptr
 
 LN_EPS = 1e-5
@@ -47,7 +47,7 @@ def debug_options() -> dict:
     dkv_keys=256 (8-wavefront key blocks in the dK/dV pass), lazy_softmax=0 (the textbook running-maximum recurrence in the forward
     attention instead of MCA_ATTN_LAZY_REFERENCE, the default since round 5: -9 % on that kernel, statistically indistinguishable
     from the textbook form over 8 data seeds, profiles/r05_lazy_softmax_seed_study.txt), deterministic=1 (the fixed-order forms of
-    the weight-gradient, LayerNorm-backward and row-reduction launches: FusionEngine.set_deterministic).  Kernel-level knobs: include/mca_hip_debug.h (hip.knobs)."""
+    the weight-gradient, LayerNorm-backward, row-reduction and table-gradient launches: FusionEngine.set_deterministic).  Kernel-level knobs: include/mca_hip_debug.h (hip.knobs)."""
     opts = {"overlap_wgrad": None, "group_wgrad": True, "mask_mfma": True, "dkv_keys": 128, "lazy_softmax": True,
             "onepass": None, "deterministic": False}          # onepass=0|1: the one-pass attention backward (attention_bwd1.hip); default: by size
     for item in filter(None, os.environ.get("MCA_DEBUG", "").split(",")):
@@ -439,7 +439,7 @@ class FusionEngine:
         so the figure holds whatever group_wgrad says) and over every encoder step's det_shapes()"""
         L, D, I, R, F, N, T = hip.lib(), self.D, self.I, self.R, self.F, self.N, b * self.N
         shapes = dict(tn=[(b * R, D, D), (R, D, D), (T, 2 * D, D), (T, D, I), (T, I, D), (T, D, D), (T, 3 * D, D)],
-                      ln=[(T, D)], rr=[(b * R, R), (R, R)] + ([(b * F, F)] if F else []), tab=[])
+                      ln=[(T, D)], rr=[(b * R, R), (R, R)] + ([(b * F, F)] if F else []), tab=[], emb=[])
         for s in self.enc_steps:
             for kind, more in s.det_shapes(b).items():
                 shapes[kind] += more
@@ -450,7 +450,8 @@ class FusionEngine:
             need = max(need, L.mca_gemm_tn_acc_group_det_scratch(Ns, Ks, len(ms), T, 0))
         need = max([need] + [L.mca_layernorm_bwd_det_scratch(r, c) for r, c in shapes["ln"]]
                    + [L.mca_reduce_rows_det_scratch(r, p, D) for r, p in shapes["rr"]]
-                   + [L.mca_tab_value_bwd_det_scratch(r, D) for r in shapes["tab"]])
+                   + [L.mca_tab_value_bwd_det_scratch(r, D) for r in shapes["tab"]]
+                   + [L.mca_embedding_scatter_add_det_scratch(r) for r in shapes["emb"]])
         return int(need)
 
     def _alloc_det_scratch(self, ws):
@@ -467,8 +468,8 @@ class FusionEngine:
         return reg
 
     def _sum_launch(self, ws, name, args, scratch_query, flops=0.0):
-        """The one launcher of the five entry points whose result depends on the order of a sum (mca_gemm_tn_acc,
-        mca_gemm_tn_acc_group, mca_layernorm_bwd, mca_reduce_rows, mca_tab_value_bwd).  args: the plain form's arguments up to
+        """The one launcher of the six entry points whose result depends on the order of a sum (mca_gemm_tn_acc,
+        mca_gemm_tn_acc_group, mca_layernorm_bwd, mca_reduce_rows, mca_tab_value_bwd, mca_embedding_scatter_add).  args: the plain form's arguments up to
         the stream.  Deterministic mode launches <name>_det: the same arguments + (scratch, scratch_floats) before the stream
         (hip.py), the scratch sized by <name>_det_scratch(*scratch_query()): the query's arguments are built in that mode only."""
         if not self._deterministic:
@@ -1020,14 +1021,18 @@ class FusionEngine:
 
     def _flag_inputs(self, batch):
         """bit 0: a non-finite value anywhere in an encoder input (encoders.py:197-198 checks the whole `tokens` tensor,
-        padded positions included); one launch for every modality."""
-        ts = [v[k] for v in batch.values() if isinstance(v, dict) for k in ("tokens", "values") if k in v and torch.is_tensor(v[k])]
+        padded positions included); one launch for every modality.  Integer tensors (the `tokens` of a SequenceEncoder) are
+        finite and are not scanned."""
+        ts = [v[k] for v in batch.values() if isinstance(v, dict) for k in ("tokens", "values")
+              if k in v and torch.is_tensor(v[k]) and v[k].is_floating_point()]
         self._flag_tensors(ts[:hip.MAX_MODALITIES], 1)
 
     def _raise_flag(self, bits: int):
         self.finite_flag.zero_()
         self._flag_host.zero_()
         self._flag_event = None
+        if bits & FLAG_INDEX_RANGE:
+            raise IndexError("a token index is outside its encoder's table (the lookup skipped it; the step's update is skipped)")
         if bits & 1:
             raise Exception("Tokens are not finite")                                      # encoders.py:197-198
         raise Exception("Encoder transform / fusion resulted in non-finite values")       # encoders.py:206-213

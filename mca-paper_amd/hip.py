@@ -184,6 +184,8 @@ SIGNATURES = {
     "mca_bcast_rows": (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I, _P]),
     "mca_reduce_rows": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I, _P]),
     "mca_embedding_renorm": (_I, [_P, _I64, _I, _F, _P]),
+    "mca_embedding_lookup": (_I, [_P, _I64, _I, _F, _P, _I, _I64, _I64, _P, _P, _I64, _I64, _I, _P, _P, _I, _P]),
+    "mca_embedding_scatter_add": (_I, [_P, _I64, _I64, _I64, _P, _I, _I64, _P, _I64, _I, _I64, _P]),
     "mca_tab_value_fwd": (_I, [_P, _P, _P, _P, _P, _I64, _I, _F, _F, _P]),
     "mca_tab_value_bwd": (_I, [_P, _I64, _P, _P, _P, _P, _I64, _I, _F, _P]),
     "mca_pack_masks": (_I, [_P, _P, _P, _P]),
@@ -229,6 +231,8 @@ SIGNATURES = {
     "mca_reduce_rows_det": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I, _P, _I64, _P]),
     "mca_tab_value_bwd_det_scratch": (_I64, [_I64, _I]),
     "mca_tab_value_bwd_det": (_I, [_P, _I64, _P, _P, _P, _P, _I64, _I, _F, _P, _I64, _P]),
+    "mca_embedding_scatter_add_det_scratch": (_I64, [_I64]),
+    "mca_embedding_scatter_add_det": (_I, [_P, _I64, _I64, _I64, _P, _I, _I64, _P, _I64, _I, _I64, _P, _I64, _P]),
 }
 # measurement hooks (include/mca_hip_debug.h): exported by the library, not part of the drop-in ABI
 DEBUG_SIGNATURES = {
