@@ -84,3 +84,67 @@ def step_calls(T):
     calls += [tn(T, N, K) for N, K in LAYER_GRADS]
     calls += [tn_group(T, LAYER_GRADS[:n]) for n in (4, 5, 6)]
     return calls
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Edge cases of tests/test_gemm_edges_gpu.py: tails, strides, misaligned pointers, shortest k-loops.  They are NOT part of
+# suite_calls() (the recorded dispatch table covers that list and does not change); test_gemm_plan_cpu.py asserts the kernel
+# and the property each one is listed for (test_gemm_edge_shapes_reach_what_they_are_listed_for).
+# ------------------------------------------------------------------------------------------------------------------------
+NT_FORMS = [(0, 0, 0), (0, 1, 1), (1, 0, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1)]          # (out_bf16, res, bias): the six of test_gemm_nt
+NT_FORMS_PERIODIC = [(0, 2, 0), (1, 2, 0)]                                             # ... and its two with M % 16 == 0
+F32_RES = [(0, 1, 0), (0, 1, 1)]
+PERSIST_FORMS = [(1, 0, 0), (1, 0, 1), (0, 0, 0), (0, 0, 1)]                           # modes 0 and 1, without and with bias
+
+
+def edge_nt(name, M, N, K, forms=None, lda=None, ldb=None, ldc=None, ldres=None, c_off=0, res_off=0, bias_off=0):
+    """One mca_gemm_nt edge case.  c_off is in ELEMENTS of the output (4 bytes fp32, 2 bytes bf16), res_off / bias_off in bytes."""
+    if forms is None:
+        forms = NT_FORMS + (NT_FORMS_PERIODIC if M % 16 == 0 else [])
+    return dict(name=name, M=M, N=N, K=K, forms=forms, lda=lda or K, ldb=ldb or K, ldc=ldc or N, ldres=ldres or N,
+                c_off=c_off, res_off=res_off, bias_off=bias_off)
+
+
+EDGE_NT = [
+    edge_nt("glds_tails", 130, 70, 64),                    # 128 x 128 kernel: row tail of 2, partial 4- and 8-element pieces, one k-step,
+    edge_nt("glds_tails_periodic", 144, 70, 64),           # ... row pointers 16-byte aligned only every second / fourth row
+    edge_nt("glds_strides", 130, 136, 128, lda=136, ldb=144, ldc=152, ldres=144),          # a full piece inside a partial column tile
+    edge_nt("nt256_k64", 2050, 136, 64),                   # 3-stage kernel, k-loop shorter than its prefetch distance, N and row tails
+    edge_nt("nt256_k128", 2050, 136, 128),
+    edge_nt("nt256_k64_periodic", 2064, 136, 64),
+    edge_nt("nt256_c_misaligned", 2050, 256, 128, ldc=264, c_off=1),                          # the scalar store path
+    edge_nt("nt256_res_bias_misaligned", 2050, 256, 128, ldc=264, res_off=4, bias_off=4),     # the unaligned residual path
+    edge_nt("nt256_prefetch_strided", 2050, 128, 512, forms=F32_RES, ldc=132, ldres=132),
+    edge_nt("nt256_prefetch_refused", 2050, 128, 512, forms=F32_RES, res_off=4),              # misaligned residual: no prefetch
+    edge_nt("persist_9_tiles", 2050, 128, 320, forms=PERSIST_FORMS, ldc=136),
+    edge_nt("persist_261_tiles", 2050, 3712, 320, forms=PERSIST_FORMS, ldc=3720),             # a second tile per workgroup, strided C
+    edge_nt("persist256_261_tiles", 2050, 7424, 192, forms=[(1, 0, 0)], ldc=7432),            # its shortest k-loop
+    edge_nt("encoder_projection", 2050, 512, 64, forms=[(0, 0, 1)]),                          # kp = 64, rows >= 2048: production
+]
+EDGE_NT_LNRES = [(2050, 128, 512, 132, 132)]          # (M, N, K, ldc, ldx): the smallest shape the entry point accepts
+# (rows, ip, D); the fused cases run with ldh = 2 * ip + 8 and ldg = ip + 8, the unfused pair takes packed rows only
+EDGE_GEGLU_FWD = [(2050, 128, 192), (2050, 3712, 192), (2050, 192, 320), (2050, 72, 64)]
+EDGE_GEGLU_BWD = [(130, 72, 64), (40962, 72, 64), (40962, 128, 320), (40962, 256, 320)]          # all with ldh = 2 * ip + 8
+# (R, N, K, lda, ldb); C has ldc = K + 4
+EDGE_TN = [(70, 72, 40, 80, 48), (300, 136, 72, 144, 80), (4100, 520, 72, 528, 80), (4100, 776, 520, 784, 528)]
+# (R, [(N, K, lda, ldb)]): 26 tiles = 2 whole splits + 157 span workgroups of the minimum span (128 rows)
+EDGE_TN_GROUP = [(4100, [(776, 520, 784, 528), (520, 264, 528, 272), (264, 776, 272, 784)])]
+
+
+def edge_nt_calls(case):
+    """the plan-level calls of one EDGE_NT case, in the order of its forms"""
+    out = []
+    for ob, res, bias in case["forms"]:
+        out.append(nt(case["M"], case["N"], case["K"], out_bf16=ob, res=res, bias=bias, c_off=case["c_off"] * (2 if ob else 4), ldc=case["ldc"],
+                      res_off=case["res_off"] if res else 0, ldres=case["ldres"], bias_off=case["bias_off"] if bias else 0))
+    return out
+
+
+def edge_calls():
+    """every GEMM entry-point call of the edge tests with all knobs 0"""
+    calls = [c for case in EDGE_NT for c in edge_nt_calls(case)]
+    calls += [fused("lnres", M, N, K) for M, N, K, _, _ in EDGE_NT_LNRES]
+    calls += [fused("geglu_fwd", *s) for s in EDGE_GEGLU_FWD] + [fused("geglu_bwd", *s) for s in EDGE_GEGLU_BWD]
+    calls += [tn(R, N, K) for R, N, K, _, _ in EDGE_TN]
+    calls += [tn_group(R, ms) for R, ms in EDGE_TN_GROUP]
+    return calls

@@ -175,6 +175,85 @@ def test_gemm_test_shapes_have_the_properties_their_comments_claim(H):
         assert l["group"]["span"] == 0 and l["grid"][0] == l["group"]["n_full"] * l["group"]["tiles"]
 
 
+def test_gemm_edge_shapes_reach_what_they_are_listed_for(H):
+    """the edge cases of tests/test_gemm_edges_gpu.py (gemm_shapes.EDGE_*), 256 CUs, all knobs 0"""
+    one = lambda call, **kn: planned_launches(H, call, 256, kn)[1]
+    name = lambda family, ob, res, tail: f"{family}<{'true' if ob else 'false'},{res},{tail}>"
+    cases = {c["name"]: c for c in GS.EDGE_NT}
+    assert len(cases) == len(GS.EDGE_NT)
+    kernels = lambda case: [one(c)[0] for c in GS.edge_nt_calls(cases[case])]
+    forms = lambda case: cases[case]["forms"]
+    # the 128 x 128 kernel: one or two k-steps, a row tail, a column tile that ends inside a 4- and an 8-element piece (70) or
+    # right behind a whole one (136 = 128 + 8); with ld = 70 a row's pointer is 16-byte aligned every second (fp32) / fourth (bf16) row
+    for case in ("glds_tails", "glds_tails_periodic", "glds_strides"):
+        c = cases[case]
+        assert [l["kernel"] for l in kernels(case)] == [name("gemm_nt_glds_kernel", ob, res, "64,0") for ob, res, _ in forms(case)]
+        assert c["M"] < 2048 and c["M"] % 128 in (2, 16) and c["N"] % 128 in (70, 8) and c["K"] in (64, 128)
+    assert cases["glds_tails"]["ldc"] * 4 % 16 == 8 and cases["glds_tails"]["ldc"] * 2 % 16 == 12 and len(forms("glds_tails")) == 6
+    assert len(forms("glds_tails_periodic")) == 8 and 70 % 4 and 70 % 8 and 136 % 128 == 8
+    c = cases["glds_strides"]
+    assert c["K"] < c["lda"] < c["ldb"] and c["N"] < c["ldres"] < c["ldc"] and all(l["grid"] == [4, 1] for l in kernels("glds_strides"))
+    # the 3-stage 256-row kernel with one and two k-steps (it prefetches two ahead), N tail 8 and row tail 2; misaligned C,
+    # residual and bias leave it on the plain <.., 0, 0> forms
+    for case in ("nt256_k64", "nt256_k128", "nt256_k64_periodic", "nt256_c_misaligned", "nt256_res_bias_misaligned", "encoder_projection"):
+        c = cases[case]
+        assert [l["kernel"] for l in kernels(case)] == [name("gemm_nt_256_kernel", ob, res, "0,0") for ob, res, _ in forms(case)], case
+        assert c["K"] // 64 <= 2 and c["M"] >= 2048 and all(l["grid"] == [(c["M"] + 255) // 256 * ((c["N"] + 127) // 128), 1] for l in kernels(case))
+    assert len(forms("nt256_k64")) == 6 and len(forms("nt256_k64_periodic")) == 8 and cases["nt256_k64"]["N"] % 128 == 8
+    # ... which an aligned C with the same strides would not all be: the planner's c16 / res16 branches decide
+    c = cases["nt256_c_misaligned"]
+    assert c["c_off"] == 1 and c["ldc"] % 8 == 0 and cases["nt256_res_bias_misaligned"]["res_off"] % 16 == 4
+    assert one(GS.nt(2050, 256, 320, out_bf16=1, ldc=264))[0]["kernel"] == "gemm_nt_persist256_kernel<false>"
+    assert one(GS.nt(2050, 256, 320, out_bf16=1, ldc=264, c_off=2))[0]["kernel"] == "gemm_nt_256_kernel<true,0,0,0>"
+    # the residual prefetch, with strides; a misaligned residual falls back to the form without it
+    assert {l["kernel"] for l in kernels("nt256_prefetch_strided")} == {"gemm_nt_256_kernel<false,1,1,0>"}
+    assert {l["kernel"] for l in kernels("nt256_prefetch_refused")} == {"gemm_nt_256_kernel<false,1,0,0>"}
+    assert cases["nt256_prefetch_strided"]["ldc"] == 132 == cases["nt256_prefetch_strided"]["ldres"]
+    # the 256 x 128 persistent kernel, modes 0 and 1 without and with bias: 9 tiles, and 261 on a grid of 256
+    want = ["gemm_nt_persist_kernel<0,false>", "gemm_nt_persist_kernel<0,true>", "gemm_nt_persist_kernel<1,false>", "gemm_nt_persist_kernel<1,true>"]
+    for case, tiles in (("persist_9_tiles", 9), ("persist_261_tiles", 261)):
+        ls = kernels(case)
+        assert [l["kernel"] for l in ls] == want and all(l["ints"][4] == tiles and l["grid"] == [min(tiles, 256), 1] for l in ls)
+        assert cases[case]["ldc"] == cases[case]["N"] + 8 and cases[case]["K"] == 320          # its shortest k-loop
+    (l,) = kernels("persist256_261_tiles")
+    assert l["kernel"] == "gemm_nt_persist256_kernel<false>" and l["ints"][4] == 261 and l["grid"] == [256, 1] and cases["persist256_261_tiles"]["K"] == 192
+    # fused LayerNorm residual: the smallest shape the entry point takes
+    (M, N, K, _, _), = GS.EDGE_NT_LNRES
+    assert one(GS.fused("lnres", M, N, K))[0]["kernel"] == "gemm_nt_256_kernel<false,1,1,2>"
+    for smaller in ((2047, N, K), (M, N - 64, K), (M, N, K - 64)):
+        assert plan_call(H, GS.fused("lnres", *smaller))[0] == -3
+    # fused GEGLU forward: the 256 x 256 kernel with 9 and 261 tiles, mode 4, and the unfused pair (the plain GEMM over both halves)
+    got = [one(GS.fused("geglu_fwd", *s))[0] for s in GS.EDGE_GEGLU_FWD]
+    assert [l["kernel"] for l in got] == ["gemm_nt_persist256_kernel<true>", "gemm_nt_persist256_kernel<true>", "gemm_nt_persist_kernel<4,false>",
+                                          "gemm_nt_256_kernel<true,0,0,0>"]
+    assert [l["ints"][4] for l in got[:3]] == [9, 261, 27] and got[3]["ints"][1] == 2 * 72
+    assert plan_call(H, GS.fused("geglu_fwd", *GS.EDGE_GEGLU_FWD[3]))[1].kernel == 0
+    # fused GEGLU backward: 128 x 128 with an ip tail, the 256-row kernel, persistent mode 3 with 161 and 322 tiles
+    got = [one(GS.fused("geglu_bwd", *s))[0] for s in GS.EDGE_GEGLU_BWD]
+    assert [l["kernel"] for l in got] == ["gemm_nt_glds_kernel<true,0,64,1>", "gemm_nt_256_kernel<true,0,0,1>", "gemm_nt_persist_kernel<3,false>",
+                                          "gemm_nt_persist_kernel<3,false>"]
+    assert got[0]["grid"] == [2, 1] and got[2]["ints"][4] == 161 and got[3]["ints"][4] == 322 and got[3]["grid"] == [256, 1]
+    # weight gradients: fewer rows than one split; 2 splits x 2 tiles; 17 splits, the last one of 4 rows, N tail 8; 12 tiles, both tails
+    got = [one(GS.tn(R, N, K))[0] for R, N, K, _, _ in GS.EDGE_TN]
+    assert [l["kernel"] for l in got] == ["gemm_tn_kernel", "gemm_tn_kernel", "gemm_tn_256_kernel", "gemm_tn_256x256_kernel"]
+    assert got[0]["grid"] == [1, 1] and got[0]["ints"][4] > 70
+    assert got[1]["grid"] == [2, 2]
+    assert got[2]["grid"][1] == 17 and 4100 - 16 * got[2]["ints"][4] == 4 and 520 % 256 == 8
+    assert got[3]["grid"][0] == 12 and 776 % 256 == 8 and 520 % 256 == 8
+    # grouped: 26 tiles = 2 whole splits of 1,664 rows + 157 span workgroups of the minimum span (the 26 x 772 rows left); knob 3: uniform splits
+    (R, ms), = GS.EDGE_TN_GROUP
+    (l,) = one(GS.tn_group(R, ms))
+    g = l["group"]
+    assert l["kernel"] == "gemm_tn_256x256_group_kernel" and (g["tiles"], g["n_full"], g["span"]) == (26, 2, 128)
+    assert l["grid"][0] - g["n_full"] * g["tiles"] == 157 == -(-26 * (R - 2 * g["unit"]) // 128)
+    (l,) = one(GS.tn_group(R, ms), **{"3": GS.TN_GROUP_UNIFORM_SPLITS})
+    assert l["group"]["span"] == 0 and l["grid"][0] == l["group"]["n_full"] * 26
+    # every kernel family is reached by an edge case as well
+    fam = {k.split("<")[0] for k in reached(H, GS.edge_calls())}
+    assert fam == {"gemm_nt_glds_kernel", "gemm_nt_256_kernel", "gemm_nt_persist_kernel", "gemm_nt_persist256_kernel", "gemm_tn_kernel",
+                   "gemm_tn_256_kernel", "gemm_tn_256x256_kernel", "gemm_tn_256x256_group_kernel"}
+
+
 def test_knob_only_kernels_are_selected_by_their_knob(H):
     assert reached(H, [GS.nt(4100, 1536, 320, res=1), GS.nt(4100, 1536, 320, res=1, bias=1)], knobs={7: 3}) == KNOB_ONLY
 
