@@ -403,8 +403,11 @@ int mca_attn_bwd_onepass(const mca_attn_bwd1_args* args, mca_stream_t stream);
  * mca_attn_bwd_prep.  Optional (q_hm and do_hm both or neither): head-major packed copies q_hm / do_hm [batch][heads][n][64] of
  * q (read with q_bstride / q_ld) and d_o - the one-pass kernel then reads a 64-row tile of a head as 8 KiB of contiguous memory
  * (pass them as its q / d_o with q_bstride = heads*n*64, q_hstride = n*64, q_ld = 64: the form the pipelined kernel takes; other
- * strides run the plain form of the same algorithm).  Both buffers need 64 rows (8 KiB) of readable slack behind the last row:
- * the kernel reads whole 64-row tiles.                                                                                    */
+ * strides run the plain form of the same algorithm).  Both buffers need 64 rows (8 KiB) of slack behind the last row that hold
+ * FINITE values of ordinary magnitude (the engine zero-fills them once): the pipelined kernel reads whole 64-row tiles without
+ * clamping to a tile's rows, and the rows past them (the next tile's, the next head's, or the slack) enter the products behind row
+ * constants of -inf, i.e. with P = 0 and dS = 0 * (finite) = 0 - a NaN or an Inf there would poison dK / dV (0 * NaN).  Their
+ * values do not change a result bit (tests/test_attention_edges_gpu.py runs zeros against randn).                          */
 int mca_attn_bwd_prep_onepass(const uint16_t* o, const uint16_t* d_o, int64_t o_bstride, int64_t o_ld, const float* lse,
                               const int32_t* row_slot, float* rowc, float* dvmean, int batch, int heads, int n, int n_qtiles,
                               const uint16_t* q, int64_t q_bstride, int64_t q_ld, uint16_t* q_hm, uint16_t* do_hm,

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-
+import attention_edge_util as EU
 
 pytestmark = pytest.mark.gpu
 C2 = 0.125 * 1.4426950408889634          # scale * log2(e): what the engine folds into the forward copy of W_q
@@ -184,6 +184,15 @@ def _attention_case(H, st, b, heads, pool, seed, drop_first, prescaled=True, spi
     rdq = q4r.grad.permute(0, 2, 1, 3).reshape(b, nq, D)
     rdk = k4r.grad.permute(0, 2, 1, 3).reshape(b, N, D)
     rdv = v4r.grad.permute(0, 2, 1, 3).reshape(b, N, D)
+    # ... and the backward ISOLATED from the forward (tests/attention_edge_util.py): float64 gradients from the stored operands and
+    # the o, lse, delta and dvmean the kernels are given, every element within its derived bound and every row within half of its
+    # bound's norm - what the global norms below cannot see (a 64-row tile 10 % off, one row with an lse off by 0.05)
+    iso = None
+    if prescaled:
+        q_st = EU.heads4(qsrc[None], 1, heads) if pool else EU.heads4(qkv[:, :, :D], b, heads)
+        iso = EU.backward_ref(q_st, k4.double(), v4.double(), EU.heads4(d_o, b, heads), lse, delta, EU.heads4(dvmean[:, None], b, heads),
+                              (~allowed)[None, None] | pad[:, None, None, :], scale=0.125)
+        iso_f32 = dict(iso, dq_bound=iso["dq_bound"] - (EU.R - EU.F32_OUT) * iso["dq"].abs())          # (the fp32 dq form is not rounded to bf16)
 
     # ---- backward in two passes without atomics: dq written once (bf16 and fp32 forms)
     for dq_f32 in (False, True):
@@ -206,6 +215,9 @@ def _attention_case(H, st, b, heads, pool, seed, drop_first, prescaled=True, spi
         e_q, e_k, e_v = rel(dq2.float(), rdq), rel(dkv2[:, :, D:2 * D].float(), rdk), rel(dkv2[:, :, 2 * D:].float(), rdv)
         assert e_q < 1.5e-2 and e_k < 1.5e-2 and e_v < 1.5e-2, f"two-pass backward rel err dq {e_q} dk {e_k} dv {e_v} (dq_f32={dq_f32})"
         assert (dkv2[:, :, :D] == 0).all()
+        if iso is not None:
+            EU.check_backward(EU.heads4(dq2, b, heads), EU.heads4(dkv2[:, :, D:2 * D], b, heads), EU.heads4(dkv2[:, :, 2 * D:], b, heads),
+                              iso_f32 if dq_f32 else iso, f"two-pass backward (dq_f32={dq_f32})", label="workload shapes, two-pass")
         # bitwise reproducible: a second launch gives the same bits
         dq3 = torch.empty_like(dq2); dkv3 = torch.zeros_like(dkv2)
         a2.dq, a2.dk, a2.dv = dq3.data_ptr(), dkv3.data_ptr() + D * 2, dkv3.data_ptr() + 2 * D * 2
@@ -265,6 +277,9 @@ def _attention_case(H, st, b, heads, pool, seed, drop_first, prescaled=True, spi
                 e_q, e_k, e_v = rel(rep[0].float(), rdq), rel(rep[1][:, :, D:2 * D].float(), rdk), rel(rep[1][:, :, 2 * D:].float(), rdv)
                 assert e_q < 1.5e-2 and e_k < 1.5e-2 and e_v < 1.5e-2, f"one-pass backward rel err dq {e_q} dk {e_k} dv {e_v} (aligned={aligned})"
                 assert (rep[1][:, :, :D] == 0).all()
+            # (the first result, element by element and row by row; delta: mca_attn_bwd_prep's, which _run_onepass compares the row constants with)
+            EU.check_backward(EU.heads4(got[0][0], b, heads), EU.heads4(got[0][1][:, :, D:2 * D], b, heads), EU.heads4(got[0][1][:, :, 2 * D:], b, heads),
+                              iso, f"one-pass backward (aligned={aligned})", label="workload shapes, one-pass")
             assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])          # a second launch: the same bits
             d_q, d_k, d_v = rel(got[0][0].float(), ref2[0]), rel(got[0][1][:, :, D:2 * D].float(), ref2[1]), rel(got[0][1][:, :, 2 * D:].float(), ref2[2])
             assert d_q < 6e-3 and d_k < 6e-3 and d_v < 6e-3, f"one-pass vs two-pass: dq {d_q} dk {d_k} dv {d_v} (aligned={aligned})"
