@@ -27,9 +27,9 @@ import numpy as np
 import torch
 
 from . import attention, hip
-from .attention import AttnGrads, AttnOperands, _OnePassSched, _Sched, _dev
+from .attention import AttnGrads, AttnKeys, AttnOperands, _OnePassSched, _Sched, _dev
 from .encoder_steps import FLAG_INDEX_RANGE, step_for
-from .hip import AttnBwd1Args, AttnBwd2Args, AttnFp8BwdOperands, AttnFp8Operands, AttnFwdArgs, LossTerm, call, ptr, stream_ptr
+from .hip import AttnFp8BwdOperands, AttnFp8Operands, LossTerm, call, ptr, stream_ptr
 
 LN_EPS = 1e-5
 FWD_BQ, FWD_BK = 128, 64
@@ -545,98 +545,38 @@ class FusionEngine:
                              self.qblk_pool, self.sched_pool_f, self.sched_pool_b2, None),
                 AttnGrads(ws["dop"], ws["delta_p"], ws["dqp32"].data_ptr(), R * D, D, True, ws["dkvp"], 0, D, 2 * D))
 
-    def _attn_common(self, a, ops, ws, q=None):
-        """the fields AttnFwdArgs, AttnBwd2Args and AttnBwd1Args share (q: another (pointer, batch stride, leading dimension))"""
-        a.q, a.q_bstride, a.q_ld = q or (ops.q, ops.q_bstride, ops.q_ld)
-        kv = ops.kv.data_ptr()
-        a.k, a.v, a.kv_bstride, a.kv_ld = kv + ops.k_off * 2, kv + ops.v_off * 2, self.N * ops.kv_ld, ops.kv_ld
-        a.keyinfo, a.ktile_flags = ws["keyinfo"].data_ptr(), ws["kflags"].data_ptr()
-        if ws.get("khot") is not None:
-            a.khot = ws["khot"].data_ptr()
-            if hasattr(a, "qblk"):
-                a.qblk = ops.qblk.data_ptr()
-        a.batch, a.heads, a.nk_pad, a.scale, a.flags = ws["b"], self.H, self.nk_pad, self.scale, self.attn_flags
-        return a
+    def attn_keys(self, ws) -> AttnKeys:
+        """the key-side state of this workspace's forward (read at every call: a test may take ws["khot"] away between two)"""
+        return AttnKeys(ws["keyinfo"], ws["kflags"], ws.get("khot"), self.N, self.nk_pad, ws["b"], self.H, self.scale, self.attn_flags)
 
     def attn_forward(self, ops, ws):
-        N, b, sched = self.N, ws["b"], ops.sched_f
-        a = self._attn_common(AttnFwdArgs(), ops, ws)
-        a.o, a.o_bstride, a.o_ld = ops.o.data_ptr(), ops.nq * ops.o.stride(0), ops.o.stride(0)
-        a.lse, a.qmask, a.vmean = ops.lse.data_ptr(), ops.qmask.data_ptr(), ws["vmean"].data_ptr()
-        a.q_ptr, a.q_kt, a.q_order = sched.q_ptr.data_ptr(), sched.q_kt.data_ptr(), sched.q_order.data_ptr()
-        a.nq, a.nk, a.n_qtiles, a.n_ktiles = ops.nq, N, sched.s.n_q, sched.s.n_k
+        N, b = self.N, ws["b"]
+        a = attention.fwd_args(ops, self.attn_keys(ws), ws["vmean"])
         # mean(V) is the output of fully masked rows only: samples with every modality present have none and are skipped
         if ws.get("present_cur") is not None:
             call("mca_attn_vmean_if_needed", a.v, a.kv_bstride, a.kv_ld, ws["vmean"].data_ptr(), b, N, self.H, ptr(ws["present_cur"]),
                  (1 << self.M) - 1, stream_ptr())
         else:
             call("mca_attn_vmean", a.v, a.kv_bstride, a.kv_ld, ws["vmean"].data_ptr(), b, N, self.H, stream_ptr())
-        hip.set_tag("pool" if ops.nq != N else "layer")
+        f = None
         if self.attn_dtype == "fp8" and ops.nq == N:
             f = self._fp8_operands(ws, b, ops.layer)[1]
             ws[("fp8gen", ops.layer)] = ws["gen"]
-            call("mca_attn_quant_mxfp8", a.q, a.q_bstride, a.q_ld, a.k, a.v, a.kv_bstride, a.kv_ld, C.byref(f), b, self.H, N, stream_ptr())
-            call("mca_attn_fwd_fp8", C.byref(a), C.byref(f), stream_ptr(), flops=4.0 * 64 * sched.s.allowed_pairs * self.H * b)
-        else:
-            call("mca_attn_fwd", C.byref(a), stream_ptr(), flops=4.0 * 64 * sched.s.allowed_pairs * self.H * b)
-        hip.set_tag("")
+        attention.launch_forward(a, ops, f)
 
     def attn_backward(self, ops, grads, ws):
-        """The attention backward in the form backward_plan names.  Two-pass (attention_bwd2.hip): dq (bf16 or fp32) is WRITTEN,
-        not accumulated.  The layer attention at a batch that gives every CU a (sample, head) takes the one-pass form."""
-        N, b, nq, sched_f, sched_b = self.N, ws["b"], ops.nq, ops.sched_f, ops.sched_b
-        plan = self.backward_plan(ws, b, nq, grads.dq_f32)
+        """The attention backward in the form backward_plan names.  The layer attention at a batch that gives every CU a
+        (sample, head) takes the one-pass form."""
+        b, keys = ws["b"], self.attn_keys(ws)
+        plan = self.backward_plan(ws, b, ops.nq, grads.dq_f32)
         if plan.form == "onepass":
-            return self._attn_backward_onepass(ops, grads, ws, plan.split)
-        o, d_o = ops.o, grads.d_o
-        call("mca_attn_bwd_prep", o.data_ptr(), d_o.data_ptr(), nq * o.stride(0), o.stride(0), ops.lse.data_ptr(),
-             grads.delta.data_ptr(), ws["dvmean"].data_ptr(), b, self.H, nq, N, stream_ptr())
-        a = self._attn_common(AttnBwd2Args(), ops, ws)
-        a.d_o, a.o_bstride, a.o_ld = d_o.data_ptr(), nq * d_o.stride(0), d_o.stride(0)
-        a.lse, a.delta, a.dvmean = ops.lse.data_ptr(), grads.delta.data_ptr(), ws["dvmean"].data_ptr()
-        a.dq, a.dq_bstride, a.dq_ld, a.dq_f32 = grads.dq, grads.dq_bstride, grads.dq_ld, int(grads.dq_f32)
-        dkv = grads.dkv.data_ptr()
-        a.dk, a.dv, a.dkv_bstride, a.dkv_ld = dkv + grads.dk_off * 2, dkv + grads.dv_off * 2, N * grads.dkv_ld, grads.dkv_ld
-        a.qmask = ops.qmask.data_ptr()
-        a.q_ptr, a.q_kt, a.q_order = sched_f.q_ptr.data_ptr(), sched_f.q_kt.data_ptr(), sched_f.q_order.data_ptr()
-        a.n_qtiles128, a.n_ktiles64 = sched_f.s.n_q, sched_f.s.n_k
-        a.k_wg, a.k_qt, a.n_qtiles64, a.n_kblocks256 = sched_b.k_wg.data_ptr(), sched_b.k_qt.data_ptr(), sched_b.s.n_q, sched_b.s.n_k
-        a.nq, a.nk, a.kblock_keys = nq, N, sched_b.s.bk
-        pairs = sched_b.s.allowed_pairs
-        hip.set_tag("pool" if nq != N else "layer")
-        # algorithmic flops of the whole backward (2 x forward) split 3 : 5 over the passes by their share of the five
-        # products a one-pass backward needs (dq pass: S, dP, dQ minus the recomputed S, dP counted once)
-        if plan.form == "fp8-twopass":
-            f, which = self._fp8_bwd_operands(ws, b, ops.layer)
-            call("mca_attn_quant_bwd_mxfp8", a.q, a.q_bstride, a.q_ld, a.k, a.v, a.kv_bstride, a.kv_ld, a.d_o, a.o_bstride, a.o_ld,
-                 C.byref(f), which, b, self.H, N, stream_ptr())
-            call("mca_attn_bwd_dkv_fp8", C.byref(a), C.byref(f), stream_ptr(), flops=8.0 * 64 * pairs * self.H * b * 0.6)
-            call("mca_attn_bwd_dq_fp8", C.byref(a), C.byref(f), stream_ptr(), flops=8.0 * 64 * pairs * self.H * b * 0.4)
+            sc = self.sched_onepass
+            assert ws["dq_acc"].numel() >= b * self.H * plan.split * (sc.n_qt + 1) * 4096, "dq_acc of this workspace is too small for the split"
+            attention.backward_onepass(ops, grads, keys, sc, ws["rowc"], ws["dq_acc"], ws["dvmean"], ws["q_hm"], ws["do_hm"], plan.split)
+        elif plan.form == "fp8-twopass":
+            attention.backward_twopass(ops, grads, keys, ws["dvmean"], *self._fp8_bwd_operands(ws, b, ops.layer))
         else:
-            call("mca_attn_bwd_dkv", C.byref(a), stream_ptr(), flops=8.0 * 64 * pairs * self.H * b * 0.6)
-            call("mca_attn_bwd_dq", C.byref(a), stream_ptr(), flops=8.0 * 64 * pairs * self.H * b * 0.4)
-        hip.set_tag("")
-
-    def _attn_backward_onepass(self, ops, grads, ws, split):
-        """one-pass backward of the layer attention (attention_bwd1.hip): dq, dk, dv bf16, every element written"""
-        N, H, b, sc, o = self.N, self.H, ws["b"], self.sched_onepass, ops.o
-        assert ws["dq_acc"].numel() >= b * H * split * (sc.n_qt + 1) * 4096, "dq_acc of this workspace is too small for the split"
-        call("mca_attn_bwd_prep_onepass", o.data_ptr(), grads.d_o.data_ptr(), N * o.stride(0), o.stride(0), ops.lse.data_ptr(),
-             sc.row_slot.data_ptr(), ws["rowc"].data_ptr(), ws["dvmean"].data_ptr(), b, H, N, sc.n_qt, ops.q, ops.q_bstride, ops.q_ld,
-             ws["q_hm"].data_ptr(), ws["do_hm"].data_ptr(), stream_ptr())
-        a = self._attn_common(AttnBwd1Args(), ops, ws, q=(ws["q_hm"].data_ptr(), H * N * 64, 64))
-        a.q_hstride = N * 64
-        a.d_o, a.o_bstride, a.o_hstride, a.o_ld = ws["do_hm"].data_ptr(), H * N * 64, N * 64, 64
-        a.rowc, a.dvmean, a.dq_acc = ws["rowc"].data_ptr(), ws["dvmean"].data_ptr(), ws["dq_acc"].data_ptr()
-        a.dq, a.dq_bstride, a.dq_ld = grads.dq, grads.dq_bstride, grads.dq_ld
-        dkv = grads.dkv.data_ptr()
-        a.dk, a.dv, a.dkv_bstride, a.dkv_ld = dkv + grads.dk_off * 2, dkv + grads.dv_off * 2, N * grads.dkv_ld, grads.dkv_ld
-        a.qt_desc, a.kb_desc, a.kb_qt, a.visit = sc.qt_desc.data_ptr(), sc.kb_desc.data_ptr(), sc.kb_qt.data_ptr(), sc.visit.data_ptr()
-        a.n_qtiles, a.n_kblocks, a.max_list, a.n_entries = sc.n_qt, sc.n_kb, sc.max_list, sc.n_entries
-        a.n, a.n_ktiles64, a.split = N, (N + 63) // 64, split
-        hip.set_tag("layer")
-        call("mca_attn_bwd_onepass", C.byref(a), stream_ptr(), flops=8.0 * 64 * sc.s.allowed_pairs * H * b)
-        hip.set_tag("")
+            attention.backward_twopass(ops, grads, keys, ws["dvmean"])
 
     # ------------------------------------------------------------------------------------------------
     # forward

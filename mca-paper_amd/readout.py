@@ -12,7 +12,7 @@ from typing import Dict, Iterable, List, Optional
 import numpy as np
 import torch
 
-from . import hip
+from . import attention, hip
 from .structure import FusionStructure
 
 
@@ -44,18 +44,7 @@ def slot_mass(pool_mass: torch.Tensor, slots: Dict[object, int]) -> Dict[object,
 
 def launch(engine, ops, ws, mass: torch.Tensor, um: torch.Tensor, probs: Optional[torch.Tensor] = None, row0: int = 0):
     """one mca_attn_readout launch on the operands of an attention whose forward has run (ops: attention.AttnOperands)"""
-    sched = ops.sched_f
-    a = hip.AttnReadoutArgs()
-    a.q, a.q_bstride, a.q_ld = ops.q, ops.q_bstride, ops.q_ld
-    a.k, a.kv_bstride, a.kv_ld = ops.kv.data_ptr() + ops.k_off * 2, engine.N * ops.kv_ld, ops.kv_ld
-    a.lse, a.qmask = ops.lse.data_ptr(), ops.qmask.data_ptr()
-    a.keyinfo, a.ktile_flags = ws["keyinfo"].data_ptr(), ws["kflags"].data_ptr()
-    a.q_ptr, a.q_kt, a.q_order = sched.q_ptr.data_ptr(), sched.q_kt.data_ptr(), sched.q_order.data_ptr()
-    a.batch, a.heads, a.nq, a.nk, a.nk_pad = ws["b"], engine.H, ops.nq, engine.N, engine.nk_pad
-    a.n_qtiles, a.n_ktiles, a.scale, a.flags = sched.s.n_q, sched.s.n_k, engine.scale, hip.ATTN_Q_PRESCALED
-    a.n_groups, a.uniform_mass, a.mass = um.numel(), um.data_ptr(), mass.data_ptr()
-    if probs is not None:
-        a.probs, a.row0, a.n_rows = probs.data_ptr(), row0, probs.shape[2]
+    a = attention.readout_args(ops, engine.attn_keys(ws), um, mass, probs, row0)
     hip.call("mca_attn_readout", C.byref(a), hip.stream_ptr())
 
 

@@ -67,7 +67,7 @@ def context(H, case, variant, pool):
         c["q_ptr"], c["q_bstride"], c["q_ld"] = c["qsrc_f"].data_ptr(), 0, D + WIDER
     else:
         c["q_ptr"], c["q_bstride"], c["q_ld"] = c["qkv_f"].data_ptr(), c["kv_bstride"], c["kv_ld"]
-    c["k_ptr"], c["v_ptr"] = c["qkv_f"].data_ptr() + D * 2, c["qkv_f"].data_ptr() + 2 * D * 2
+    c["v_ptr"] = c["qkv_f"].data_ptr() + 2 * D * 2
     c["sf"] = att._Sched(st.pool_schedule(128, 64) if pool else st.attn_schedule(128, 64), DEV)
     c["sb"] = {bk: att._Sched(st.pool_schedule(64, bk) if pool else st.attn_schedule(64, bk), DEV) for bk in (256, 128)}
     c["qmask"] = torch.from_numpy(c["qmask_np"].astype(np.uint32).view(np.int32)).to(DEV)
@@ -83,6 +83,11 @@ def context(H, case, variant, pool):
     qb[:, 15] = 0
     c["qblk"] = torch.where(qb == 1, 0.0, -32768.0).to(torch.bfloat16).contiguous()
     c["vmean"] = nan_f32(b, D)
+    # the records the builders of attention.py take; the framed operands go in through the stride fields, o / lse per launch
+    c["att"] = att
+    c["keys"] = att.AttnKeys(c["keyinfo"], c["kflags"], c["khot"], N, nk_pad, b, heads, U.SCALE, H.ATTN_Q_PRESCALED)
+    c["ops"] = att.AttnOperands(c["q_ptr"], c["q_bstride"], c["q_ld"], c["qkv_f"], D, 2 * D, c["kv_ld"], None, None, nq, c["qmask"], c["qblk"],
+                                c["sf"], None, None)
     H.call("mca_attn_vmean", c["v_ptr"], c["kv_bstride"], c["kv_ld"], c["vmean"].data_ptr(), b, N, heads, H.stream_ptr())
     torch.cuda.synchronize()
     assert torch.equal(c["kflags"].cpu(), torch.from_numpy(AC.ktile_flags(c["pad"].cpu().numpy())))          # the restated rule IS the kernel's
@@ -94,6 +99,7 @@ def context(H, case, variant, pool):
     c["fwd_ref"] = U.forward_ref(c["q4"], c["k4"], c["v4"], c["blk"])
     # the forward whose o / lse the backward is given: the register-staged form
     c["o"], c["lse"] = run_forward(H, c, khot=False, lazy=False)
+    c["ops"] = c["ops"]._replace(o=c["o"].t, lse=c["lse"])
     c["o4"] = U.heads4(c["o"].t, b)
     # mca_attn_bwd_prep on them
     c["delta"], c["dvmean"] = nan_f32(b, heads, nq), nan_f32(b, D)
@@ -109,17 +115,8 @@ def run_forward(H, c, khot, lazy):
     b, N, D, nq, heads = c["b"], c["N"], c["D"], c["nq"], c["heads"]
     o = G.guarded_out(b * nq, D, D + WIDER, torch.bfloat16, device=DEV)
     lse = nan_f32(b, heads, nq)
-    a, sf = H.AttnFwdArgs(), c["sf"]
-    a.q, a.q_bstride, a.q_ld = c["q_ptr"], c["q_bstride"], c["q_ld"]
-    a.k, a.v, a.kv_bstride, a.kv_ld = c["k_ptr"], c["v_ptr"], c["kv_bstride"], c["kv_ld"]
-    a.o, a.o_bstride, a.o_ld, a.lse = o.data_ptr(), c["o_bstride"], c["o_ld"], lse.data_ptr()
-    a.qmask, a.keyinfo, a.ktile_flags = c["qmask"].data_ptr(), c["keyinfo"].data_ptr(), c["kflags"].data_ptr()
-    a.q_ptr, a.q_kt, a.q_order = sf.q_ptr.data_ptr(), sf.q_kt.data_ptr(), sf.q_order.data_ptr()
-    a.vmean = c["vmean"].data_ptr()
-    a.batch, a.heads, a.nq, a.nk, a.nk_pad, a.n_qtiles, a.n_ktiles, a.scale = b, heads, nq, N, c["nk_pad"], sf.s.n_q, sf.s.n_k, U.SCALE
-    a.flags = H.ATTN_Q_PRESCALED | (H.ATTN_LAZY_REFERENCE if lazy else 0)
-    if khot:
-        a.khot = c["khot"].data_ptr()
+    keys = c["keys"]._replace(khot=c["khot"] if khot else None, flags=H.ATTN_Q_PRESCALED | (H.ATTN_LAZY_REFERENCE if lazy else 0))
+    a = c["att"].fwd_args(c["ops"]._replace(o=o.t, lse=lse), keys, c["vmean"])
     H.call("mca_attn_fwd", C.byref(a), H.stream_ptr())
     torch.cuda.synchronize()
     return o, lse
@@ -127,20 +124,8 @@ def run_forward(H, c, khot, lazy):
 
 def bwd2_args(H, c, dq, dq_f32, dkv, bkeys, hot):
     b, N, D, nq, heads = c["b"], c["N"], c["D"], c["nq"], c["heads"]
-    a2, sf, sb = H.AttnBwd2Args(), c["sf"], c["sb"][bkeys]
-    a2.q, a2.q_bstride, a2.q_ld = c["q_ptr"], c["q_bstride"], c["q_ld"]
-    a2.k, a2.v, a2.kv_bstride, a2.kv_ld = c["k_ptr"], c["v_ptr"], c["kv_bstride"], c["kv_ld"]
-    a2.d_o, a2.o_bstride, a2.o_ld = c["do_f"].data_ptr(), c["o_bstride"], c["o_ld"]
-    a2.lse, a2.delta, a2.dvmean = c["lse"].data_ptr(), c["delta"].data_ptr(), c["dvmean"].data_ptr()
-    a2.dq, a2.dq_bstride, a2.dq_ld, a2.dq_f32 = dq.data_ptr(), nq * (D + WIDER), D + WIDER, int(dq_f32)
-    a2.dk, a2.dv, a2.dkv_bstride, a2.dkv_ld = dkv.data_ptr() + D * 2, dkv.data_ptr() + 2 * D * 2, N * (3 * D + WIDER), 3 * D + WIDER
-    a2.qmask, a2.keyinfo, a2.ktile_flags = c["qmask"].data_ptr(), c["keyinfo"].data_ptr(), c["kflags"].data_ptr()
-    a2.q_ptr, a2.q_kt, a2.q_order, a2.n_qtiles128, a2.n_ktiles64 = sf.q_ptr.data_ptr(), sf.q_kt.data_ptr(), sf.q_order.data_ptr(), sf.s.n_q, sf.s.n_k
-    a2.k_wg, a2.k_qt, a2.n_qtiles64, a2.n_kblocks256, a2.kblock_keys = sb.k_wg.data_ptr(), sb.k_qt.data_ptr(), sb.s.n_q, sb.s.n_k, (128 if bkeys == 128 else 0)
-    a2.batch, a2.heads, a2.nq, a2.nk, a2.nk_pad, a2.scale, a2.flags = b, heads, nq, N, c["nk_pad"], U.SCALE, H.ATTN_Q_PRESCALED
-    if hot:
-        a2.khot, a2.qblk = c["khot"].data_ptr(), c["qblk"].data_ptr()
-    return a2
+    grads = c["att"].AttnGrads(c["do_f"], c["delta"], dq.data_ptr(), nq * (D + WIDER), D + WIDER, dq_f32, dkv.t, D, 2 * D, 3 * D + WIDER)
+    return c["att"].bwd2_args(c["ops"], grads, c["keys"] if hot else c["keys"]._replace(khot=None), c["dvmean"], c["sb"][bkeys])
 
 
 def new_dq(c, f32=False):
@@ -300,23 +285,13 @@ def run_onepass(H, c, sc, prep, packed, split=0):
     nqt = prep["nqt"]
     dq, dkv = new_dq(c), new_dkv(c)
     acc = nan_f32(b * heads * max(1, split) * (nqt + 1) * 4096)
-    a1 = H.AttnBwd1Args()
-    a1.k, a1.v, a1.kv_bstride, a1.kv_ld = c["k_ptr"], c["v_ptr"], c["kv_bstride"], c["kv_ld"]
+    att = c["att"]
     if packed:
-        a1.q, a1.q_bstride, a1.q_hstride, a1.q_ld = prep["bufs"][0].data_ptr(), heads * N * 64, N * 64, 64
-        a1.d_o, a1.o_bstride, a1.o_hstride, a1.o_ld = prep["bufs"][1].data_ptr(), heads * N * 64, N * 64, 64
+        src = [att.RowSource(x.data_ptr(), heads * N * 64, N * 64, 64) for x in prep["bufs"]]
     else:
-        a1.q, a1.q_bstride, a1.q_ld = c["q_ptr"], c["q_bstride"], c["q_ld"]
-        a1.d_o, a1.o_bstride, a1.o_ld = c["do_f"].data_ptr(), c["o_bstride"], c["o_ld"]
-    a1.rowc, a1.dvmean = prep["rowc"].data_ptr(), prep["dvmean"].data_ptr()
-    a1.dq, a1.dq_bstride, a1.dq_ld = dq.data_ptr(), N * (D + WIDER), D + WIDER
-    a1.dk, a1.dv, a1.dkv_bstride, a1.dkv_ld = dkv.data_ptr() + D * 2, dkv.data_ptr() + 2 * D * 2, N * (3 * D + WIDER), 3 * D + WIDER
-    a1.dq_acc = acc.data_ptr()
-    a1.keyinfo, a1.ktile_flags, a1.khot, a1.qblk = c["keyinfo"].data_ptr(), c["kflags"].data_ptr(), c["khot"].data_ptr(), c["qblk"].data_ptr()
-    a1.qt_desc, a1.kb_desc, a1.kb_qt, a1.visit = sc.qt_desc.data_ptr(), sc.kb_desc.data_ptr(), sc.kb_qt.data_ptr(), sc.visit.data_ptr()
-    a1.n_qtiles, a1.n_kblocks, a1.max_list, a1.n_entries = sc.n_qt, sc.n_kb, sc.max_list, sc.n_entries
-    a1.batch, a1.heads, a1.n, a1.nk_pad, a1.n_ktiles64 = b, heads, N, c["nk_pad"], (N + 63) // 64
-    a1.scale, a1.flags, a1.split = U.SCALE, H.ATTN_Q_PRESCALED, split
+        src = [att.RowSource(c["q_ptr"], c["q_bstride"], 0, c["q_ld"]), att.RowSource(c["do_f"].data_ptr(), c["o_bstride"], 0, c["o_ld"])]
+    grads = att.AttnGrads(c["do_f"], None, dq.data_ptr(), N * (D + WIDER), D + WIDER, False, dkv.t, D, 2 * D, 3 * D + WIDER)
+    a1 = att.bwd1_args(c["ops"], grads, c["keys"], sc, prep["rowc"], acc, prep["dvmean"], split, *src)
     H.call("mca_attn_bwd_onepass", C.byref(a1), H.stream_ptr())          # (a refusal raises: at these sizes the tables always fit)
     torch.cuda.synchronize()
     G.assert_guard_intact(dq, "dq")

@@ -46,15 +46,15 @@ def _attention_case(H, st, b, heads, pool, seed, drop_first, prescaled=True, spi
     dense reference sees q = q' / (scale * log2 e), and dq is the gradient w.r.t. that q.  spike: a few keys 40x larger, so
     that the lazy softmax reference of the forward kernel has to move mid-row (at a row's later tiles, up and from a very
     negative start) - cdna guide rule 26: a rare data-dependent branch needs an input that forces it."""
-    eng = importlib.import_module("mca-paper_amd.engine")
+    A = importlib.import_module("mca-paper_amd.attention")
     N, D = st.n_tokens, heads * 64
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(seed)
     qmask_np = st.qmask_pool if pool else st.qmask_attn
     nq = len(qmask_np)
-    sf = eng._Sched(st.pool_schedule(128, 64) if pool else st.attn_schedule(128, 64), dev)
-    sb = eng._Sched(st.pool_schedule(64, 256) if pool else st.attn_schedule(64, 256), dev)
-    sb128 = eng._Sched(st.pool_schedule(64, 128) if pool else st.attn_schedule(64, 128), dev)          # the dkv pass's 4-wavefront form
+    sf = A._Sched(st.pool_schedule(128, 64) if pool else st.attn_schedule(128, 64), dev)
+    sb = A._Sched(st.pool_schedule(64, 256) if pool else st.attn_schedule(64, 256), dev)
+    sb128 = A._Sched(st.pool_schedule(64, 128) if pool else st.attn_schedule(64, 128), dev)          # the dkv pass's 4-wavefront form
     qmask = torch.from_numpy(qmask_np.astype(np.uint32).view(np.int32)).to(dev)
     kgroup = torch.from_numpy(st.kgroup).to(dev)
     allowed = torch.from_numpy(~(st.dense_pool_mask() if pool else st.dense_attn_mask())).to(dev)
@@ -98,18 +98,11 @@ def _attention_case(H, st, b, heads, pool, seed, drop_first, prescaled=True, spi
     assert rel(vmean, qkv[:, :, 2 * D:].float().mean(1)) < 1e-5
     o = torch.zeros(b * nq, D, dtype=torch.bfloat16, device=dev)
     lse = torch.empty(b, heads, nq, device=dev)
-    a = H.AttnFwdArgs()
-    if pool:
-        a.q, a.q_bstride, a.q_ld = qsrc.data_ptr(), 0, D
-    else:
-        a.q, a.q_bstride, a.q_ld = qkv.data_ptr(), N * 3 * D, 3 * D
-    a.k, a.v, a.kv_bstride, a.kv_ld = qkv.data_ptr() + D * 2, vptr, N * 3 * D, 3 * D
-    a.o, a.o_bstride, a.o_ld, a.lse = o.data_ptr(), nq * D, D, lse.data_ptr()
-    a.qmask, a.keyinfo, a.ktile_flags = qmask.data_ptr(), keyinfo.data_ptr(), kflags.data_ptr()
-    a.q_ptr, a.q_kt, a.q_order = sf.q_ptr.data_ptr(), sf.q_kt.data_ptr(), sf.q_order.data_ptr()
-    a.vmean = vmean.data_ptr()
-    a.batch, a.heads, a.nq, a.nk, a.nk_pad, a.n_qtiles, a.n_ktiles, a.scale = b, heads, nq, N, nk_pad, sf.s.n_q, sf.s.n_k, 0.125
-    a.flags = H.ATTN_Q_PRESCALED if prescaled else 0
+    # (the element-wise mask first: no one-hot operand, qblk comes with the backward's mask product)
+    keys = A.AttnKeys(keyinfo, kflags, None, N, nk_pad, b, heads, 0.125, H.ATTN_Q_PRESCALED if prescaled else 0)
+    ops = A.AttnOperands(qsrc.data_ptr() if pool else qkv.data_ptr(), 0 if pool else N * 3 * D, D if pool else 3 * D, qkv, D, 2 * D, 3 * D,
+                         o, lse, nq, qmask, None, sf, sb, None)
+    a = A.fwd_args(ops, keys, vmean)
     H.call("mca_attn_fwd", C.byref(a), H.stream_ptr())
     torch.cuda.synchronize()
     got_o = o.float().view(b, nq, D)
@@ -198,17 +191,8 @@ def _attention_case(H, st, b, heads, pool, seed, drop_first, prescaled=True, spi
     for dq_f32 in (False, True):
         dq2 = torch.full((b, nq, D), 7.0, device=dev, dtype=torch.float32 if dq_f32 else torch.bfloat16)          # no pre-zeroing needed
         dkv2 = torch.zeros(b, N, 3 * D, dtype=torch.bfloat16, device=dev)
-        a2 = H.AttnBwd2Args()
-        a2.q, a2.q_bstride, a2.q_ld = a.q, a.q_bstride, a.q_ld
-        a2.k, a2.v, a2.kv_bstride, a2.kv_ld = a.k, a.v, a.kv_bstride, a.kv_ld
-        a2.d_o, a2.o_bstride, a2.o_ld = d_o.data_ptr(), nq * D, D
-        a2.lse, a2.delta, a2.dvmean = lse.data_ptr(), delta.data_ptr(), dvmean.data_ptr()
-        a2.dq, a2.dq_bstride, a2.dq_ld, a2.dq_f32 = dq2.data_ptr(), nq * D, D, int(dq_f32)
-        a2.dk, a2.dv, a2.dkv_bstride, a2.dkv_ld = dkv2.data_ptr() + D * 2, dkv2.data_ptr() + 2 * D * 2, N * 3 * D, 3 * D
-        a2.qmask, a2.keyinfo, a2.ktile_flags = qmask.data_ptr(), keyinfo.data_ptr(), kflags.data_ptr()
-        a2.q_ptr, a2.q_kt, a2.q_order, a2.n_qtiles128, a2.n_ktiles64 = sf.q_ptr.data_ptr(), sf.q_kt.data_ptr(), sf.q_order.data_ptr(), sf.s.n_q, sf.s.n_k
-        a2.k_wg, a2.k_qt, a2.n_qtiles64, a2.n_kblocks256 = sb.k_wg.data_ptr(), sb.k_qt.data_ptr(), sb.s.n_q, sb.s.n_k
-        a2.batch, a2.heads, a2.nq, a2.nk, a2.nk_pad, a2.scale, a2.flags = b, heads, nq, N, nk_pad, 0.125, a.flags
+        grads = A.AttnGrads(d_o.view(b * nq, D), delta, dq2.data_ptr(), nq * D, D, dq_f32, dkv2, D, 2 * D, 3 * D)
+        a2 = A.bwd2_args(ops, grads, keys, dvmean)          # (256-key blocks, the element-wise mask)
         H.call("mca_attn_bwd_dq", C.byref(a2), H.stream_ptr())
         H.call("mca_attn_bwd_dkv", C.byref(a2), H.stream_ptr())
         torch.cuda.synchronize()
@@ -258,7 +242,7 @@ def _attention_case(H, st, b, heads, pool, seed, drop_first, prescaled=True, spi
             sc_ = S_.build_onepass_schedule(qmask_np, st.kgroup, 64, 256, aligned)
             too_big = len(sc_.qt_desc) >= 256 or len(sc_.kb_desc) > 64 or int(sc_.kb_desc[:, 3].max()) + 6 > 256 or len(sc_.kb_qt) + 4 * len(sc_.kb_desc) > 768
             try:
-                got = _run_onepass(H, sc_, b, heads, N, nk_pad, qkv, o, d_o, lse, dvmean, keyinfo, kflags, khot, qblk)
+                got = _run_onepass(H, sc_, ops._replace(qblk=qblk), keys._replace(khot=khot), d_o, dvmean)
             except H.MCAHipError as exc:          # tables past the kernel's LDS budget: refused, the caller keeps the two-pass form
                 assert too_big and "unsupported" in str(exc), str(exc)
                 continue
@@ -288,12 +272,15 @@ def _attention_case(H, st, b, heads, pool, seed, drop_first, prescaled=True, spi
             assert rel(outs[0][0].float(), outs[1][0].float()) < 6e-3
 
 
-def _run_onepass(H, sc, b, heads, N, nk_pad, qkv, o, d_o, lse, dvmean_ref, keyinfo, kflags, khot, qblk):
-    """mca_attn_bwd_prep_onepass + mca_attn_bwd_onepass on the tables `sc`, twice; returns [(dq, dkv), (dq, dkv)]"""
+def _run_onepass(H, sc, ops, keys, d_o, dvmean_ref):
+    """mca_attn_bwd_prep_onepass + mca_attn_bwd_onepass on the tables `sc` and the operands of a layer attention whose forward has
+    run (ops: q | k | v in one (b, N, 3 * heads * 64) matrix, qblk set; keys: with the one-hot operand), twice; returns
+    [(dq, dkv), (dq, dkv)]"""
+    A = importlib.import_module("mca-paper_amd.attention")
+    b, heads, N, qkv, o, lse = keys.batch, keys.heads, keys.nk, ops.kv, ops.o, ops.lse
     dev, D = "cuda", heads * 64
-    i32 = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.int32) if x.dtype == np.uint32 else np.ascontiguousarray(x)).to(dev)
-    qt_desc, kb_desc, kb_qt, visit, row_slot = i32(sc.qt_desc), i32(sc.kb_desc), i32(sc.kb_qt), i32(sc.visit), i32(sc.row_slot)
-    nqt, nkb = len(sc.qt_desc), len(sc.kb_desc)
+    sched = A._OnePassSched(sc, dev)
+    row_slot, nqt = sched.row_slot, sched.n_qt
     rowc = torch.empty(b, heads, nqt + 1, 2, 64, device=dev)          # (+ the null tile)
     rowc[:, :, :, 0] = float("-inf"); rowc[:, :, :, 1] = 0.0
     dvmean = torch.full_like(dvmean_ref, 3.0)
@@ -318,23 +305,12 @@ def _run_onepass(H, sc, b, heads, N, nk_pad, qkv, o, d_o, lse, dvmean_ref, keyin
     for rep_i in range(2):          # first launch: q / dO from the (b, n, heads*64) matrices; second: from the packed copies (same bits)
         dq = torch.full((b, N, D), 7.0, device=dev, dtype=torch.bfloat16)
         dkv = torch.zeros(b, N, 3 * D, dtype=torch.bfloat16, device=dev)
-        a1 = H.AttnBwd1Args()
-        a1.k, a1.v, a1.kv_bstride, a1.kv_ld = qkv.data_ptr() + D * 2, qkv.data_ptr() + 2 * D * 2, N * 3 * D, 3 * D
         if rep_i == 0:
-            a1.q, a1.q_bstride, a1.q_ld = qkv.data_ptr(), N * 3 * D, 3 * D
-            a1.d_o, a1.o_bstride, a1.o_ld = d_o.data_ptr(), N * D, D
+            src = A.RowSource(qkv.data_ptr(), N * 3 * D, 0, 3 * D), A.RowSource(d_o.data_ptr(), N * D, 0, D)
         else:
-            a1.q, a1.q_bstride, a1.q_hstride, a1.q_ld = q_hm.data_ptr(), heads * N * 64, N * 64, 64
-            a1.d_o, a1.o_bstride, a1.o_hstride, a1.o_ld = do_hm.data_ptr(), heads * N * 64, N * 64, 64
-        a1.rowc, a1.dvmean = rowc.data_ptr(), dvmean.data_ptr()
-        a1.dq, a1.dq_bstride, a1.dq_ld = dq.data_ptr(), N * D, D
-        a1.dk, a1.dv, a1.dkv_bstride, a1.dkv_ld = dkv.data_ptr() + D * 2, dkv.data_ptr() + 2 * D * 2, N * 3 * D, 3 * D
-        a1.dq_acc = acc.data_ptr()
-        a1.keyinfo, a1.ktile_flags, a1.khot, a1.qblk = keyinfo.data_ptr(), kflags.data_ptr(), khot.data_ptr(), qblk.data_ptr()
-        a1.qt_desc, a1.kb_desc, a1.kb_qt, a1.visit = qt_desc.data_ptr(), kb_desc.data_ptr(), kb_qt.data_ptr(), visit.data_ptr()
-        a1.n_qtiles, a1.n_kblocks, a1.max_list, a1.n_entries = nqt, nkb, int(sc.kb_desc[:, 3].max()), int(len(sc.kb_qt))
-        a1.batch, a1.heads, a1.n, a1.nk_pad, a1.n_ktiles64 = b, heads, N, nk_pad, (N + 63) // 64
-        a1.scale, a1.flags = 0.125, H.ATTN_Q_PRESCALED
+            src = A.RowSource(q_hm.data_ptr(), heads * N * 64, N * 64, 64), A.RowSource(do_hm.data_ptr(), heads * N * 64, N * 64, 64)
+        grads = A.AttnGrads(d_o.view(b * N, D), None, dq.data_ptr(), N * D, D, False, dkv, D, 2 * D, 3 * D)
+        a1 = A.bwd1_args(ops, grads, keys, sched, rowc, acc, dvmean, 0, *src)
         H.call("mca_attn_bwd_onepass", C.byref(a1), H.stream_ptr())
         torch.cuda.synchronize()
         out.append((dq, dkv))
@@ -514,7 +490,7 @@ def test_attention_fp8_forward(H, shape):
     The quantised operands themselves are compared value for value."""
     from oracle import mca_oracle as O
     S = importlib.import_module("mca-paper_amd.structure")
-    eng = importlib.import_module("mca-paper_amd.engine")
+    A = importlib.import_module("mca-paper_amd.attention")
     if shape == "small":
         st, b, heads = S.FusionStructure([70, 45, 30], 8, (3, 2), fcl=True), 3, 2
     elif shape == "cmu":
@@ -524,7 +500,7 @@ def test_attention_fp8_forward(H, shape):
     dev = "cuda"
     N, D = st.n_tokens, heads * 64
     g = torch.Generator(device=dev).manual_seed(21)
-    sf = eng._Sched(st.attn_schedule(128, 64), dev)
+    sf = A._Sched(st.attn_schedule(128, 64), dev)
     qmask = torch.from_numpy(st.qmask_attn.astype(np.uint32).view(np.int32)).to(dev)
     kgroup = torch.from_numpy(st.kgroup).to(dev)
     allowed = torch.from_numpy(~st.dense_attn_mask()).to(dev)
@@ -569,15 +545,8 @@ def test_attention_fp8_forward(H, shape):
     # ---- forward
     o = torch.zeros(b * N, D, dtype=torch.bfloat16, device=dev)
     lse = torch.empty(b, heads, N, device=dev)
-    a = H.AttnFwdArgs()
-    a.q, a.q_bstride, a.q_ld = qkv.data_ptr(), N * 3 * D, 3 * D
-    a.k, a.v, a.kv_bstride, a.kv_ld = qkv.data_ptr() + D * 2, vptr, N * 3 * D, 3 * D
-    a.o, a.o_bstride, a.o_ld, a.lse = o.data_ptr(), N * D, D, lse.data_ptr()
-    a.qmask, a.keyinfo, a.ktile_flags = qmask.data_ptr(), keyinfo.data_ptr(), kflags.data_ptr()
-    a.q_ptr, a.q_kt, a.q_order = sf.q_ptr.data_ptr(), sf.q_kt.data_ptr(), sf.q_order.data_ptr()
-    a.vmean = vmean.data_ptr()
-    a.batch, a.heads, a.nq, a.nk, a.nk_pad, a.n_qtiles, a.n_ktiles, a.scale = b, heads, N, N, nk_pad, sf.s.n_q, sf.s.n_k, 0.125
-    a.flags = H.ATTN_Q_PRESCALED
+    keys = A.AttnKeys(keyinfo, kflags, None, N, nk_pad, b, heads, 0.125, H.ATTN_Q_PRESCALED)
+    a = A.fwd_args(A.AttnOperands(qkv.data_ptr(), N * 3 * D, 3 * D, qkv, D, 2 * D, 3 * D, o, lse, N, qmask, None, sf, None, None), keys, vmean)
     H.call("mca_attn_fwd_fp8", C.byref(a), C.byref(f), H.stream_ptr())
     torch.cuda.synchronize()
     # the mask as a matrix product (mca_build_keyhot): the same bits
@@ -612,7 +581,7 @@ def test_attention_fp8_backward(H, shape):
     input).  Bitwise repeatable."""
     from oracle import mca_oracle as O
     S = importlib.import_module("mca-paper_amd.structure")
-    eng = importlib.import_module("mca-paper_amd.engine")
+    A = importlib.import_module("mca-paper_amd.attention")
     if shape == "small":
         st, b, heads = S.FusionStructure([70, 45, 30], 8, (3, 2), fcl=True), 3, 2
     elif shape == "cmu":
@@ -622,8 +591,8 @@ def test_attention_fp8_backward(H, shape):
     dev = "cuda"
     N, D = st.n_tokens, heads * 64
     g = torch.Generator(device=dev).manual_seed(23)
-    sf = eng._Sched(st.attn_schedule(128, 64), dev)
-    sb = eng._Sched(st.attn_schedule(64, 128), dev)
+    sf = A._Sched(st.attn_schedule(128, 64), dev)
+    sb = A._Sched(st.attn_schedule(64, 128), dev)
     qmask = torch.from_numpy(st.qmask_attn.astype(np.uint32).view(np.int32)).to(dev)
     bits = (st.qmask_attn.astype(np.uint32)[:, None] >> np.arange(16, dtype=np.uint32)[None, :]) & 1
     bits[:, 15] = 0
@@ -663,16 +632,9 @@ def test_attention_fp8_backward(H, shape):
     H.call("mca_attn_quant_mxfp8", qkv.data_ptr(), N * 3 * D, 3 * D, kptr, vptr, N * 3 * D, 3 * D, C.byref(f), b, heads, N, H.stream_ptr())
     o = torch.zeros(b * N, D, dtype=torch.bfloat16, device=dev)
     lse = torch.empty(b, heads, N, device=dev)
-    a = H.AttnFwdArgs()
-    a.q, a.q_bstride, a.q_ld = qkv.data_ptr(), N * 3 * D, 3 * D
-    a.k, a.v, a.kv_bstride, a.kv_ld = kptr, vptr, N * 3 * D, 3 * D
-    a.o, a.o_bstride, a.o_ld, a.lse = o.data_ptr(), N * D, D, lse.data_ptr()
-    a.qmask, a.keyinfo, a.ktile_flags = qmask.data_ptr(), keyinfo.data_ptr(), kflags.data_ptr()
-    a.q_ptr, a.q_kt, a.q_order = sf.q_ptr.data_ptr(), sf.q_kt.data_ptr(), sf.q_order.data_ptr()
-    a.vmean, a.khot = vmean.data_ptr(), khot.data_ptr()
-    a.batch, a.heads, a.nq, a.nk, a.nk_pad, a.n_qtiles, a.n_ktiles, a.scale = b, heads, N, N, nk_pad, sf.s.n_q, sf.s.n_k, 0.125
-    a.flags = H.ATTN_Q_PRESCALED
-    H.call("mca_attn_fwd_fp8", C.byref(a), C.byref(f), H.stream_ptr())
+    keys = A.AttnKeys(keyinfo, kflags, khot, N, nk_pad, b, heads, 0.125, H.ATTN_Q_PRESCALED)
+    ops = A.AttnOperands(qkv.data_ptr(), N * 3 * D, 3 * D, qkv, D, 2 * D, 3 * D, o, lse, N, qmask, qblk, sf, sb, None)
+    H.call("mca_attn_fwd_fp8", C.byref(A.fwd_args(ops, keys, vmean)), C.byref(f), H.stream_ptr())
     # ---- backward
     delta = torch.empty(b, heads, N, device=dev)
     dvmean = torch.empty(b, D, device=dev)
@@ -696,18 +658,7 @@ def test_attention_fp8_backward(H, shape):
 
     def run():
         dqkv.zero_()
-        a2 = H.AttnBwd2Args()
-        a2.q, a2.q_bstride, a2.q_ld = qkv.data_ptr(), N * 3 * D, 3 * D
-        a2.k, a2.v, a2.kv_bstride, a2.kv_ld = kptr, vptr, N * 3 * D, 3 * D
-        a2.d_o, a2.o_bstride, a2.o_ld = d_o.data_ptr(), N * D, D
-        a2.lse, a2.delta, a2.dvmean = lse.data_ptr(), delta.data_ptr(), dvmean.data_ptr()
-        a2.dq, a2.dq_bstride, a2.dq_ld, a2.dq_f32 = dqkv.data_ptr(), N * 3 * D, 3 * D, 0
-        a2.dk, a2.dv, a2.dkv_bstride, a2.dkv_ld = dqkv.data_ptr() + D * 2, dqkv.data_ptr() + 2 * D * 2, N * 3 * D, 3 * D
-        a2.qmask, a2.keyinfo, a2.ktile_flags = qmask.data_ptr(), keyinfo.data_ptr(), kflags.data_ptr()
-        a2.q_ptr, a2.q_kt, a2.q_order, a2.n_qtiles128, a2.n_ktiles64 = sf.q_ptr.data_ptr(), sf.q_kt.data_ptr(), sf.q_order.data_ptr(), sf.s.n_q, sf.s.n_k
-        a2.k_wg, a2.k_qt, a2.n_qtiles64, a2.n_kblocks256 = sb.k_wg.data_ptr(), sb.k_qt.data_ptr(), sb.s.n_q, sb.s.n_k
-        a2.batch, a2.heads, a2.nq, a2.nk, a2.nk_pad, a2.scale, a2.flags = b, heads, N, N, nk_pad, 0.125, H.ATTN_Q_PRESCALED
-        a2.khot, a2.qblk, a2.kblock_keys = khot.data_ptr(), qblk.data_ptr(), 128
+        a2 = A.bwd2_args(ops, A.AttnGrads(d_o, delta, dqkv.data_ptr(), N * 3 * D, 3 * D, False, dqkv, D, 2 * D, 3 * D), keys, dvmean)          # (128-key blocks)
         H.call("mca_attn_bwd_dkv_fp8", C.byref(a2), C.byref(fo), H.stream_ptr())
         H.call("mca_attn_bwd_dq_fp8", C.byref(a2), C.byref(fo), H.stream_ptr())
         torch.cuda.synchronize()

@@ -138,21 +138,12 @@ def build_case(H, name):
     H.call("mca_attn_vmean", vptr, N * 3 * D, 3 * D, vmean.data_ptr(), b, N, heads, H.stream_ptr())
     o = torch.zeros(b * nq, D, dtype=torch.bfloat16, device=DEV)
     c.lse = torch.empty(b, heads, nq, device=DEV)
-    a = H.AttnFwdArgs()
-    if pool:
-        a.q, a.q_bstride, a.q_ld = c.qsrc.data_ptr(), 0, D
-    else:
-        a.q, a.q_bstride, a.q_ld = qkv.data_ptr(), N * 3 * D, 3 * D
-    a.k, a.v, a.kv_bstride, a.kv_ld = qkv.data_ptr() + D * 2, vptr, N * 3 * D, 3 * D
-    a.o, a.o_bstride, a.o_ld, a.lse = o.data_ptr(), nq * D, D, c.lse.data_ptr()
-    a.qmask, a.keyinfo, a.ktile_flags = c.qmask.data_ptr(), c.keyinfo.data_ptr(), c.kflags.data_ptr()
-    a.q_ptr, a.q_kt, a.q_order = c.sf.q_ptr.data_ptr(), c.sf.q_kt.data_ptr(), c.sf.q_order.data_ptr()
-    a.vmean = vmean.data_ptr()
-    a.batch, a.heads, a.nq, a.nk, a.nk_pad, a.n_qtiles, a.n_ktiles, a.scale = b, heads, nq, N, c.nk_pad, c.sf.s.n_q, c.sf.s.n_k, 0.125
-    a.flags = H.ATTN_Q_PRESCALED
-    H.call("mca_attn_fwd", C.byref(a), H.stream_ptr())
+    c.A = A
+    c.keys = A.AttnKeys(c.keyinfo, c.kflags, None, N, c.nk_pad, b, heads, 0.125, H.ATTN_Q_PRESCALED)
+    c.ops = A.AttnOperands(c.qsrc.data_ptr() if pool else qkv.data_ptr(), 0 if pool else N * 3 * D, D if pool else 3 * D, qkv, D, 2 * D, 3 * D,
+                           o, c.lse, nq, c.qmask, None, c.sf, None, None)
+    H.call("mca_attn_fwd", C.byref(A.fwd_args(c.ops, c.keys, vmean)), H.stream_ptr())
     torch.cuda.synchronize()
-    c.fwd = a
     # the forward marks exactly the dense reference's uniform rows, and its lse is the dense one (the forward test's bound)
     assert torch.equal(torch.isinf(c.lse), c.uni[:, None, :].expand(-1, heads, -1))
     fin = ~torch.isinf(c.lse)
@@ -166,15 +157,8 @@ def build_case(H, name):
 
 
 def readout_args(H, c, lse, mass, probs=None, row0=0, n_rows=0):
-    a, f = H.AttnReadoutArgs(), c.fwd
-    a.q, a.q_bstride, a.q_ld, a.k, a.kv_bstride, a.kv_ld = f.q, f.q_bstride, f.q_ld, f.k, f.kv_bstride, f.kv_ld
-    a.lse, a.qmask, a.keyinfo, a.ktile_flags = lse.data_ptr(), f.qmask, f.keyinfo, f.ktile_flags
-    a.q_ptr, a.q_kt, a.q_order = f.q_ptr, f.q_kt, f.q_order
-    a.batch, a.heads, a.nq, a.nk, a.nk_pad, a.n_qtiles, a.n_ktiles = f.batch, f.heads, f.nq, f.nk, f.nk_pad, f.n_qtiles, f.n_ktiles
-    a.scale, a.flags, a.n_groups, a.uniform_mass, a.mass = 0.125, H.ATTN_Q_PRESCALED, c.G, c.um.data_ptr(), mass.data_ptr()
-    if probs is not None:
-        a.probs, a.row0, a.n_rows = probs.data_ptr(), row0, n_rows
-    return a
+    assert probs is None or n_rows == probs.shape[2]
+    return c.A.readout_args(c.ops._replace(lse=lse), c.keys, c.um, mass, probs, row0)
 
 
 def run_readout(H, c, lse, window=None):

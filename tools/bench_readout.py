@@ -40,12 +40,7 @@ def main():
     a0["qkv"].copy_(torch.randn(a0["qkv"].shape, device="cuda", generator=g).bfloat16())
     a0["qkv"][:, :D] *= 0.18
     ops = eng.layer_attention(ws, 0)[0]
-    sched = ops.sched_f
-    fa = eng._attn_common(H.AttnFwdArgs(), ops, ws)
-    fa.o, fa.o_bstride, fa.o_ld = ops.o.data_ptr(), ops.nq * ops.o.stride(0), ops.o.stride(0)
-    fa.lse, fa.qmask, fa.vmean = ops.lse.data_ptr(), ops.qmask.data_ptr(), ws["vmean"].data_ptr()
-    fa.q_ptr, fa.q_kt, fa.q_order = sched.q_ptr.data_ptr(), sched.q_kt.data_ptr(), sched.q_order.data_ptr()
-    fa.nq, fa.nk, fa.n_qtiles, fa.n_ktiles = ops.nq, N, sched.s.n_q, sched.s.n_k
+    fa = importlib.import_module("mca-paper_amd.attention").fwd_args(ops, eng.attn_keys(ws), ws["vmean"])
     um = torch.from_numpy(RO.uniform_mass(eng.st)).cuda()
     mass = torch.empty(b, Hh, N, um.numel(), device="cuda")
 

@@ -2,7 +2,7 @@
 import importlib, os, sys, ctypes as C, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-H = importlib.import_module("mca-paper_amd.hip"); S = importlib.import_module("mca-paper_amd.structure"); E = importlib.import_module("mca-paper_amd.engine")
+H = importlib.import_module("mca-paper_amd.hip"); S = importlib.import_module("mca-paper_amd.structure"); A = importlib.import_module("mca-paper_amd.attention")
 import test_attention_gpu as T
 
 shape = sys.argv[1] if len(sys.argv) > 1 else "small"
@@ -34,28 +34,21 @@ H.call("mca_build_keyhot", keyinfo.data_ptr(), khot.data_ptr(), b, nk_pad, H.str
 bits = (torch.from_numpy(st.qmask_attn.astype(np.int64)).to(dev)[:, None] >> torch.arange(16, device=dev)[None, :]) & 1
 bits[:, 15] = 0
 qblk = torch.where(bits == 1, 0.0, -32768.0).to(torch.bfloat16).contiguous()
-sf = E._Sched(st.attn_schedule(128, 64), dev)
+sf = A._Sched(st.attn_schedule(128, 64), dev)
 qmask = torch.from_numpy(st.qmask_attn.astype(np.uint32).view(np.int32)).to(dev)
 vmean = torch.empty(b, D, device=dev)
 H.call("mca_attn_vmean", qkv.data_ptr() + 2 * D * 2, N * 3 * D, 3 * D, vmean.data_ptr(), b, N, heads, H.stream_ptr())
 o = torch.zeros(b * N, D, dtype=torch.bfloat16, device=dev); lse = torch.empty(b, heads, N, device=dev)
-a = H.AttnFwdArgs()
-a.q, a.q_bstride, a.q_ld = qkv.data_ptr(), N * 3 * D, 3 * D
-a.k, a.v, a.kv_bstride, a.kv_ld = qkv.data_ptr() + D * 2, qkv.data_ptr() + 2 * D * 2, N * 3 * D, 3 * D
-a.o, a.o_bstride, a.o_ld, a.lse = o.data_ptr(), N * D, D, lse.data_ptr()
-a.qmask, a.keyinfo, a.ktile_flags = qmask.data_ptr(), keyinfo.data_ptr(), kflags.data_ptr()
-a.q_ptr, a.q_kt, a.q_order = sf.q_ptr.data_ptr(), sf.q_kt.data_ptr(), sf.q_order.data_ptr()
-a.vmean = vmean.data_ptr()
-a.batch, a.heads, a.nq, a.nk, a.nk_pad, a.n_qtiles, a.n_ktiles, a.scale = b, heads, N, N, nk_pad, sf.s.n_q, sf.s.n_k, 0.125
-a.flags, a.khot = H.ATTN_Q_PRESCALED, khot.data_ptr()
-H.call("mca_attn_fwd", C.byref(a), H.stream_ptr())
+keys = A.AttnKeys(keyinfo, kflags, khot, N, nk_pad, b, heads, 0.125, H.ATTN_Q_PRESCALED)
+ops = A.AttnOperands(qkv.data_ptr(), N * 3 * D, 3 * D, qkv, D, 2 * D, 3 * D, o, lse, N, qmask, qblk, sf, None, None)
+H.call("mca_attn_fwd", C.byref(A.fwd_args(ops, keys, vmean)), H.stream_ptr())
 d_o = T.bf(torch.randn(b, N, D, device=dev, generator=g))
 dvmean = torch.zeros(b, D, device=dev)
 sc = S.build_onepass_schedule(st.qmask_attn, st.kgroup, 64, 256, True)
 print("q tiles", sc.qt_desc.tolist()); print("key blocks", sc.kb_desc.tolist())
 with H.knobs(k9=64):
-    ref = T._run_onepass(H, sc, b, heads, N, nk_pad, qkv, o, d_o, lse, dvmean, keyinfo, kflags, khot, qblk)[0]
-got = T._run_onepass(H, sc, b, heads, N, nk_pad, qkv, o, d_o, lse, dvmean, keyinfo, kflags, khot, qblk)[0]
+    ref = T._run_onepass(H, sc, ops, keys, d_o, dvmean)[0]
+got = T._run_onepass(H, sc, ops, keys, d_o, dvmean)[0]
 rel = lambda x, y: float((x.float() - y.float()).norm() / (y.float().norm() + 1e-30))
 print("dq", rel(got[0], ref[0]), "dk", rel(got[1][:, :, D:2 * D], ref[1][:, :, D:2 * D]), "dv", rel(got[1][:, :, 2 * D:], ref[1][:, :, 2 * D:]))
 for hh in range(heads):
@@ -87,8 +80,8 @@ for t, (r0, rn) in enumerate(sc.qt_desc.tolist()):
 print("---- repeat 6x each kernel, NaN counts (dq, dkv):")
 for rep in range(6):
     with H.knobs(k9=64):
-        r_ = T._run_onepass(H, sc, b, heads, N, nk_pad, qkv, o, d_o, lse, dvmean, keyinfo, kflags, khot, qblk)
-    g_ = T._run_onepass(H, sc, b, heads, N, nk_pad, qkv, o, d_o, lse, dvmean, keyinfo, kflags, khot, qblk)
+        r_ = T._run_onepass(H, sc, ops, keys, d_o, dvmean)
+    g_ = T._run_onepass(H, sc, ops, keys, d_o, dvmean)
     cnt = lambda t: int(torch.isnan(t.float()).sum())
     print("plain", [(cnt(x[0]), cnt(x[1])) for x in r_], "pipelined", [(cnt(x[0]), cnt(x[1])) for x in g_])
     for name, outs in (("plain", r_), ("pipelined", g_)):
@@ -99,7 +92,7 @@ for rep in range(6):
                 print("   ", name, "NaN samples", sorted(set(i_[:, 0].tolist())), "keys", sorted(set(i_[:, 1].tolist()))[:12], "..", "col blocks", sorted(set((i_[:, 2] // 64).tolist())))
 print("---- NaN positions (flat element offsets) over 12 launches of the pipelined kernel")
 for rep in range(12):
-    g_ = T._run_onepass(H, sc, b, heads, N, nk_pad, qkv, o, d_o, lse, dvmean, keyinfo, kflags, khot, qblk)
+    g_ = T._run_onepass(H, sc, ops, keys, d_o, dvmean)
     for li, x in enumerate(g_):
         for nm, t in (("dq", x[0]), ("dkv", x[1])):
             f = t.view(-1).view(torch.int16)
