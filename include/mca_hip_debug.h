@@ -52,6 +52,16 @@ struct mca_tn_det_plan;
 struct mca_tn_group_det_plan;
 int mca_dbg_plan_gemm_tn_det(int64_t R, int64_t N, int64_t K, struct mca_tn_det_plan* out);
 int mca_dbg_plan_gemm_tn_group_det(const int64_t* N, const int64_t* K, int n, int64_t R, int cus, struct mca_tn_group_det_plan* out);
+/* Which LayerNorm kernel a call would launch: the planners of csrc/ln_plan.h (where the structs and the forms are defined), as
+ * mca_layernorm_fwd and mca_layernorm_bwd / _bwd_det call them, with the current knob table (12 and 14).  The problem carries every
+ * pointer as an integer: only null-ness and alignment are read.  Nothing is launched and no device is touched.  Return 0, or
+ * MCA_E_BADARG where the entry point would refuse (rows == 0 included: there is nothing to plan). */
+struct mca_ln_fwd_problem;
+struct mca_ln_fwd_plan;
+struct mca_ln_bwd_problem;
+struct mca_ln_bwd_plan;
+int mca_dbg_plan_layernorm_fwd(const struct mca_ln_fwd_problem* problem, struct mca_ln_fwd_plan* out);
+int mca_dbg_plan_layernorm_bwd(const struct mca_ln_bwd_problem* problem, struct mca_ln_bwd_plan* out);
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,8 @@ def needs_build() -> bool:
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "mca_hip.h")]
+    # every file of csrc/ (the plan headers gemm_plan.h and ln_plan.h among them) and both public headers
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", h) for h in ("mca_hip.h", "mca_hip_debug.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -2,6 +2,8 @@
 // fusions), GEGLU fwd/bwd, bf16 casts, row broadcast / row reduction.  One wavefront (64 lanes) per
 // row for the norms; 16-byte accesses wherever the layout allows.
 #include "common.h"
+#include "ln_plan.h"          // which LayerNorm kernel, which grid (plain host C++)
+#include "../../include/mca_hip_debug.h"
 
 // =====================================================================================================
 // LayerNorm forward.  Reference: model.py:24-31 (gamma only), encoders.py:189-192,199-209 (affine,
@@ -201,32 +203,26 @@ extern "C" int mca_layernorm_fwd(const float* x, int64_t ldx, const float* gamma
                                  mca_stream_t stream) {
   if (!x || !gamma || rows < 0 || cols <= 0 || cols > 1024) return MCA_E_BADARG;
   if (rows == 0) return MCA_OK;
-  if (!y && y_bf16 && !add && cols <= 256 && mca_knobs[12] != 1) {          // narrow rows, bf16 output only (knob 12 = 1: general kernel)
-    int64_t nb = (rows + 15) / 16; if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(ln_fwd_narrow_kernel, dim3((unsigned)nb), dim3(256), 0, as_stream(stream), x, ldx, gamma, beta, rowmask, y_bf16, ld_bf16,
-                       cols_pad, mean, rstd, rows, cols, eps);
-    return launch_status();
+  const mca_ln_fwd_problem pr = {rows, cols, cols_pad, ldx, ldy, y_bstride, ld_bf16, period, (uintptr_t)x, (uintptr_t)gamma, (uintptr_t)beta,
+                                 (uintptr_t)rowmask, (uintptr_t)add, (uintptr_t)y, (uintptr_t)y_bf16};
+  const mca_ln_fwd_plan p = mca_plan_layernorm_fwd(pr, mca_knobs);
+  const dim3 grid((unsigned)p.grid_x);
+#define LNF_TRUNK(NI) hipLaunchKernelGGL(ln_fwd_trunk_kernel<NI>, grid, dim3(256), 0, as_stream(stream), x, ldx, gamma, y_bf16, ld_bf16, mean, rstd, rows, cols, eps)
+#define LNF_GENERAL(VEC) hipLaunchKernelGGL(ln_fwd_kernel<VEC>, grid, dim3(256), 0, as_stream(stream), x, ldx, gamma, beta, rowmask, add, period, y, ldy, \
+                                            y_bstride, y_bf16, ld_bf16, cols_pad, mean, rstd, rows, cols, eps)
+  switch (p.form) {
+    case MCA_LN_NARROW:
+      hipLaunchKernelGGL(ln_fwd_narrow_kernel, grid, dim3(256), 0, as_stream(stream), x, ldx, gamma, beta, rowmask, y_bf16, ld_bf16, cols_pad, mean, rstd,
+                         rows, cols, eps);
+      break;
+    case MCA_LN_TRUNK:
+      if (p.width == 1) LNF_TRUNK(1); else if (p.width == 2) LNF_TRUNK(2); else LNF_TRUNK(4);
+      break;
+    default:
+      if (p.width == 4) LNF_GENERAL(4); else LNF_GENERAL(1);
   }
-  const bool vec = (cols % 4 == 0) && (ldx % 4 == 0) && (!y || (ldy % 4 == 0 && y_bstride % 4 == 0)) &&
-                   (!y_bf16 || ld_bf16 % 4 == 0) &&
-                   ((uintptr_t)x % 16 == 0) && (!y || (uintptr_t)y % 16 == 0) && (!add || (uintptr_t)add % 16 == 0);
-  if (vec && !beta && !rowmask && !add && !y && y_bf16 && cols_pad <= cols && (cols == 256 || cols == 512 || cols == 1024) &&
-      (uintptr_t)gamma % 16 == 0 && mca_knobs[12] != 1) {          // knob 12 = 1: general kernel (A/B); any row count, so that a
-                                                                   // given call form always takes the same arithmetic path
-    const unsigned nb = (unsigned)((rows + 7) / 8);
-    if (cols == 256) hipLaunchKernelGGL(ln_fwd_trunk_kernel<1>, dim3(nb), dim3(256), 0, as_stream(stream), x, ldx, gamma, y_bf16, ld_bf16, mean, rstd, rows, cols, eps);
-    else if (cols == 512) hipLaunchKernelGGL(ln_fwd_trunk_kernel<2>, dim3(nb), dim3(256), 0, as_stream(stream), x, ldx, gamma, y_bf16, ld_bf16, mean, rstd, rows, cols, eps);
-    else hipLaunchKernelGGL(ln_fwd_trunk_kernel<4>, dim3(nb), dim3(256), 0, as_stream(stream), x, ldx, gamma, y_bf16, ld_bf16, mean, rstd, rows, cols, eps);
-    return launch_status();
-  }
-  int64_t blocks = (rows + 3) / 4;
-  if (blocks > 8192) blocks = 8192;
-  if (vec)
-    hipLaunchKernelGGL(ln_fwd_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), x, ldx, gamma, beta,
-                       rowmask, add, period, y, ldy, y_bstride, y_bf16, ld_bf16, cols_pad, mean, rstd, rows, cols, eps);
-  else
-    hipLaunchKernelGGL(ln_fwd_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), x, ldx, gamma, beta,
-                       rowmask, add, period, y, ldy, y_bstride, y_bf16, ld_bf16, cols_pad, mean, rstd, rows, cols, eps);
+#undef LNF_TRUNK
+#undef LNF_GENERAL
   return launch_status();
 }
 
@@ -444,38 +440,6 @@ __global__ __launch_bounds__(256) void ln_bwd_params_kernel(const float* __restr
   }
 }
 
-// The grids of the three forms: one place for the launches and for the deterministic form's scratch need (a slot per workgroup
-// slab).  Knob 14 as described in include/mca_hip_debug.h.
-static inline int64_t ln_bwd_params_slabs(int64_t rows, int cols, int64_t* rpb_out) {
-  const int cw = cols <= 64 ? 64 : (cols <= 128 ? 128 : 256);
-  const int chunks = (cols + cw - 1) / cw;
-  int64_t slabs = 1024 / chunks;          // four rounds of workgroups at most (each ends with one atomic per column)
-  if (slabs > (rows + 31) / 32) slabs = (rows + 31) / 32;
-  if (slabs < 1) slabs = 1;
-  const int64_t rpb = (rows + slabs - 1) / slabs;
-  if (rpb_out) *rpb_out = rpb;
-  return (rows + rpb - 1) / rpb;
-}
-static inline int64_t ln_bwd_trunk_blocks(int64_t rows) {
-  // one workgroup per CU at most: every workgroup ends with one atomic per column on dgamma, and 1024 of them on the same
-  // 512 addresses cost more than the extra loads in flight bring (b = 8: 40.8 -> 28.5 us, b = 32: 108.7 -> 104.0 us;
-  // knob 14 = another cap, tools/bench_ln.py)
-  int64_t nb = (rows + 7) / 8;
-  const int64_t cap = mca_knobs[14] > 0 ? mca_knobs[14] : 256;
-  return nb > cap ? cap : nb;
-}
-static inline int64_t ln_bwd_general_blocks(int64_t rows) {
-  int64_t blocks = (rows + 3) / 4;
-  // every workgroup ends with one atomic per column on the same dgamma / dbeta / dxsum addresses, and a wavefront has one row in
-  // flight: few workgroups at few rows, up to four per CU at many (measured, tools/bench_ln_encoder.py: 3,600 rows 14.5 us at
-  // 256 against 30.7 at 1,024; 48,000 rows 134 us at 256 against 70 at 1,024)
-  int64_t bcap = rows / 32;
-  if (bcap < 256) bcap = 256;
-  if (bcap > 1024) bcap = 1024;
-  if (mca_knobs[14] > 0) bcap = mca_knobs[14];
-  return blocks > bcap ? bcap : blocks;
-}
-
 // DET: dgamma / dbeta / dxsum point at slot 0 of the scratch; *slots = the workgroup slabs that wrote a slot each
 template <bool DET>
 static int ln_bwd_launch(const float* dy, int64_t ldy, int64_t y_bstride, int64_t period,
@@ -483,40 +447,31 @@ static int ln_bwd_launch(const float* dy, int64_t ldy, int64_t y_bstride, int64_
                          const float* mean, const float* rstd, const uint8_t* rowmask,
                          float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16,
                          float* dgamma, float* dbeta, float* dxsum, int64_t rows, int cols, mca_stream_t stream, int64_t* slots) {
-  *slots = 0;
-  if (!dx && !dx_bf16 && !dxsum && mca_knobs[12] != 1) {          // parameter gradients only
-    if (!dgamma && !dbeta) return MCA_OK;
-    const int cw = cols <= 64 ? 64 : (cols <= 128 ? 128 : 256);
-    const int chunks = (cols + cw - 1) / cw;
-    int64_t rpb;
-    const dim3 grid(chunks, (unsigned)ln_bwd_params_slabs(rows, cols, &rpb));
-    *slots = grid.y;
-#define LNP_LAUNCH(CW) hipLaunchKernelGGL((ln_bwd_params_kernel<CW, DET>), grid, dim3(256), 0, as_stream(stream), dy, ldy, y_bstride, period, x, ldx, mean, rstd, \
-                                          rowmask, dgamma, dbeta, rows, cols, rpb)
-    if (cw == 64) LNP_LAUNCH(64); else if (cw == 128) LNP_LAUNCH(128); else LNP_LAUNCH(256);
-#undef LNP_LAUNCH
-    return launch_status();
+  const mca_ln_bwd_problem pr = {rows, cols, 0, ldy, y_bstride, period, ldx, lddx, ld_bf16, (uintptr_t)dy, (uintptr_t)x, (uintptr_t)gamma,
+                                 (uintptr_t)rowmask, (uintptr_t)dx, (uintptr_t)dx_bf16, (uintptr_t)dgamma, (uintptr_t)dbeta, (uintptr_t)dxsum};
+  const mca_ln_bwd_plan p = mca_plan_layernorm_bwd(pr, mca_knobs);
+  *slots = p.slots;
+  const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y);
+#define LNB_PARAMS(CW) hipLaunchKernelGGL((ln_bwd_params_kernel<CW, DET>), grid, dim3(256), 0, as_stream(stream), dy, ldy, y_bstride, period, x, ldx, mean, rstd, \
+                                          rowmask, dgamma, dbeta, rows, cols, p.rows_per_block)
+#define LNB_TRUNK(NI) hipLaunchKernelGGL((ln_bwd_trunk_kernel<NI, DET>), grid, dim3(256), 0, as_stream(stream), dy, ldy, x, ldx, gamma, mean, rstd, dx, lddx, \
+                                         dx_bf16, ld_bf16, dgamma, rows, cols)
+#define LNB_GENERAL(VEC) hipLaunchKernelGGL((ln_bwd_kernel<VEC, DET>), grid, dim3(256), 0, as_stream(stream), dy, ldy, y_bstride, period, x, ldx, gamma, mean, rstd, \
+                                            rowmask, dx, lddx, dx_bf16, ld_bf16, dgamma, dbeta, dxsum, rows, cols)
+  switch (p.form) {
+    case MCA_LN_NONE: return MCA_OK;
+    case MCA_LN_PARAMS:
+      if (p.width == 64) LNB_PARAMS(64); else if (p.width == 128) LNB_PARAMS(128); else LNB_PARAMS(256);
+      break;
+    case MCA_LN_TRUNK:
+      if (p.width == 1) LNB_TRUNK(1); else if (p.width == 2) LNB_TRUNK(2); else LNB_TRUNK(4);
+      break;
+    default:
+      if (p.width == 4) LNB_GENERAL(4); else LNB_GENERAL(1);
   }
-  const bool vec = (cols % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (y_bstride % 4 == 0) &&
-                   (!dx || lddx % 4 == 0) && (!dx_bf16 || ld_bf16 % 4 == 0) &&
-                   ((uintptr_t)x % 16 == 0) && ((uintptr_t)dy % 16 == 0) && (!dx || (uintptr_t)dx % 16 == 0);
-  if (vec && !rowmask && period <= 0 && !dbeta && !dxsum && dgamma && (cols == 256 || cols == 512 || cols == 1024) &&
-      (uintptr_t)gamma % 16 == 0 && mca_knobs[12] != 1) {          // knob 12 = 1: general kernel (A/B)
-    const int64_t nb = ln_bwd_trunk_blocks(rows);
-    *slots = nb;
-    if (cols == 256) hipLaunchKernelGGL((ln_bwd_trunk_kernel<1, DET>), dim3((unsigned)nb), dim3(256), 0, as_stream(stream), dy, ldy, x, ldx, gamma, mean, rstd, dx, lddx, dx_bf16, ld_bf16, dgamma, rows, cols);
-    else if (cols == 512) hipLaunchKernelGGL((ln_bwd_trunk_kernel<2, DET>), dim3((unsigned)nb), dim3(256), 0, as_stream(stream), dy, ldy, x, ldx, gamma, mean, rstd, dx, lddx, dx_bf16, ld_bf16, dgamma, rows, cols);
-    else hipLaunchKernelGGL((ln_bwd_trunk_kernel<4, DET>), dim3((unsigned)nb), dim3(256), 0, as_stream(stream), dy, ldy, x, ldx, gamma, mean, rstd, dx, lddx, dx_bf16, ld_bf16, dgamma, rows, cols);
-    return launch_status();
-  }
-  const int64_t blocks = ln_bwd_general_blocks(rows);
-  *slots = blocks;
-  if (vec)
-    hipLaunchKernelGGL((ln_bwd_kernel<4, DET>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), dy, ldy, y_bstride,
-                       period, x, ldx, gamma, mean, rstd, rowmask, dx, lddx, dx_bf16, ld_bf16, dgamma, dbeta, dxsum, rows, cols);
-  else
-    hipLaunchKernelGGL((ln_bwd_kernel<1, DET>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), dy, ldy, y_bstride,
-                       period, x, ldx, gamma, mean, rstd, rowmask, dx, lddx, dx_bf16, ld_bf16, dgamma, dbeta, dxsum, rows, cols);
+#undef LNB_PARAMS
+#undef LNB_TRUNK
+#undef LNB_GENERAL
   return launch_status();
 }
 
@@ -559,11 +514,7 @@ int mca_det_reduce(const float* scratch, int64_t slot_stride, int slots, float* 
 
 extern "C" int64_t mca_layernorm_bwd_det_scratch(int64_t rows, int cols) {
   if (rows <= 0 || cols <= 0 || cols > 1024) return 0;
-  int64_t slots = ln_bwd_general_blocks(rows);
-  const int64_t ps = ln_bwd_params_slabs(rows, cols, nullptr);
-  if (ps > slots) slots = ps;
-  if (cols == 256 || cols == 512 || cols == 1024) { const int64_t tb = ln_bwd_trunk_blocks(rows); if (tb > slots) slots = tb; }
-  return slots * 3 * cols;
+  return mca_plan_layernorm_bwd_det_scratch(rows, cols, mca_knobs);
 }
 extern "C" int mca_layernorm_bwd_det(const float* dy, int64_t ldy, int64_t y_bstride, int64_t period,
                                      const float* x, int64_t ldx, const float* gamma,
@@ -582,6 +533,18 @@ extern "C" int mca_layernorm_bwd_det(const float* dy, int64_t ldy, int64_t y_bst
   for (int t = 0; t < 3 && rc == MCA_OK && slots > 0; t++)
     if (target[t]) rc = mca_det_reduce(part[t], 3 * (int64_t)cols, (int)slots, target[t], cols, 1, cols, stream);
   return rc;
+}
+
+// the planners as the entry points call them (include/mca_hip_debug.h): nothing is launched, no device is touched
+extern "C" int mca_dbg_plan_layernorm_fwd(const mca_ln_fwd_problem* pr, mca_ln_fwd_plan* out) {
+  if (!pr || !out || !pr->x || !pr->gamma || pr->rows <= 0 || pr->cols <= 0 || pr->cols > 1024) return MCA_E_BADARG;
+  *out = mca_plan_layernorm_fwd(*pr, mca_knobs);
+  return MCA_OK;
+}
+extern "C" int mca_dbg_plan_layernorm_bwd(const mca_ln_bwd_problem* pr, mca_ln_bwd_plan* out) {
+  if (!pr || !out || !pr->dy || !pr->x || !pr->gamma || pr->rows <= 0 || pr->cols <= 0 || pr->cols > 1024) return MCA_E_BADARG;
+  *out = mca_plan_layernorm_bwd(*pr, mca_knobs);
+  return MCA_OK;
 }
 
 // =====================================================================================================

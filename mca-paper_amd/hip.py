@@ -158,6 +158,31 @@ class TnGroupDetPlan(C.Structure):
 
 PLAN_NT, PLAN_LNRES, PLAN_GEGLU_FWD, PLAN_GEGLU_BWD = range(4)          # `entry` of mca_dbg_plan_gemm_nt
 
+
+# the LayerNorm planners' structs (csrc/ln_plan.h; filled by mca_dbg_plan_layernorm_fwd / _bwd).  Pointers travel as integers.
+class LnFwdProblem(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("cols", C.c_int32), ("cols_pad", C.c_int32)] + \
+               [(f, C.c_int64) for f in ("ldx", "ldy", "y_bstride", "ld_bf16", "period")] + \
+               [(f, C.c_uint64) for f in ("x", "gamma", "beta", "rowmask", "add", "y", "y_bf16")]
+
+
+class LnFwdPlan(C.Structure):
+    _fields_ = [("form", C.c_int32), ("width", C.c_int32), ("grid_x", C.c_int64), ("passes", C.c_int64)]
+
+
+class LnBwdProblem(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("cols", C.c_int32), ("pad_", C.c_int32)] + \
+               [(f, C.c_int64) for f in ("ldy", "y_bstride", "period", "ldx", "lddx", "ld_bf16")] + \
+               [(f, C.c_uint64) for f in ("dy", "x", "gamma", "rowmask", "dx", "dx_bf16", "dgamma", "dbeta", "dxsum")]
+
+
+class LnBwdPlan(C.Structure):
+    _fields_ = [("form", C.c_int32), ("width", C.c_int32)] + \
+               [(f, C.c_int64) for f in ("grid_x", "grid_y", "rows_per_block", "slots", "passes")]
+
+
+LN_NONE, LN_NARROW, LN_TRUNK, LN_GENERAL, LN_PARAMS = range(5)          # `form` of the LayerNorm plans
+
 _P, _I64, _I, _F = C.c_void_p, C.c_int64, C.c_int, C.c_float
 
 # name -> (restype, argtypes).  Must list EVERY symbol include/mca_hip.h declares (tests check this).
@@ -244,6 +269,8 @@ DEBUG_SIGNATURES = {
     "mca_dbg_plan_gemm_tn_group": (_I, [C.POINTER(_I64), C.POINTER(_I64), _I, _I64, _I, C.POINTER(TnGroupPlan)]),
     "mca_dbg_plan_gemm_tn_det": (_I, [_I64, _I64, _I64, C.POINTER(TnDetPlan)]),
     "mca_dbg_plan_gemm_tn_group_det": (_I, [C.POINTER(_I64), C.POINTER(_I64), _I, _I64, _I, C.POINTER(TnGroupDetPlan)]),
+    "mca_dbg_plan_layernorm_fwd": (_I, [C.POINTER(LnFwdProblem), C.POINTER(LnFwdPlan)]),
+    "mca_dbg_plan_layernorm_bwd": (_I, [C.POINTER(LnBwdProblem), C.POINTER(LnBwdPlan)]),
 }
 
 _lib: Optional[C.CDLL] = None
