@@ -62,6 +62,11 @@ struct mca_ln_bwd_problem;
 struct mca_ln_bwd_plan;
 int mca_dbg_plan_layernorm_fwd(const struct mca_ln_fwd_problem* problem, struct mca_ln_fwd_plan* out);
 int mca_dbg_plan_layernorm_bwd(const struct mca_ln_bwd_problem* problem, struct mca_ln_bwd_plan* out);
+/* The workspace of mca_contrastive_fwd_bwd for a gathered batch of B rows and T terms, in bytes from the workspace pointer:
+ * out = {G offset, G bytes, stats offset, stats bytes, w offset, w bytes}.  G (T, B, B) fp32 holds dG after the call, stats is
+ * (T, B, 4) fp32 = {lse of row i, lse of column i, ce_row + ce_col, dsum}, w is (T, W) fp32 with room for W = B ranks.  The entry
+ * point and mca_contrastive_workspace_bytes (= w offset + w bytes + 256) place the regions by this function.  Pure host code. */
+int mca_dbg_contrastive_layout(int B, int T, int64_t* out);
 #ifdef __cplusplus
 }
 #endif

@@ -194,9 +194,21 @@ __global__ __launch_bounds__(512) void dpooled_kernel(const float* __restrict__ 
   }
 }
 
-extern "C" int64_t mca_contrastive_workspace_bytes(int B, int T) {
+// The workspace of one call, stated once: G (T, B, B), which holds dG after the call, then stats (T, B, 4), then w (T, W) with room
+// for W = B.  out = {G offset, G bytes, stats offset, stats bytes, w offset, w bytes}.  Pure host code (include/mca_hip_debug.h).
+extern "C" int mca_dbg_contrastive_layout(int B, int T, int64_t* out) {
+  if (!out) return MCA_E_BADARG;
   const int64_t g = (int64_t)T * B * B * 4, st = (int64_t)T * B * 4 * 4, w = (int64_t)T * B * 4;
-  return g + st + w + 256;
+  out[0] = 0; out[1] = g;
+  out[2] = g; out[3] = st;
+  out[4] = g + st; out[5] = w;
+  return MCA_OK;
+}
+
+extern "C" int64_t mca_contrastive_workspace_bytes(int B, int T) {
+  int64_t lay[6];
+  mca_dbg_contrastive_layout(B, T, lay);
+  return lay[4] + lay[5] + 256;
 }
 
 extern "C" int mca_contrastive_fwd_bwd(const float* pooled_all, const uint32_t* present_all, const mca_loss_term* terms,
@@ -209,9 +221,12 @@ extern "C" int mca_contrastive_fwd_bwd(const float* pooled_all, const uint32_t* 
     return MCA_E_BADARG;
   const int W = B / b_local;
   if ((size_t)3 * T * W * sizeof(float) > 60000) return MCA_E_UNSUPPORTED;
-  float* G = reinterpret_cast<float*>(workspace);
-  float* stats = G + (int64_t)T * B * B;
-  float* w = stats + (int64_t)T * B * 4;
+  int64_t lay[6];
+  mca_dbg_contrastive_layout(B, T, lay);
+  char* base = reinterpret_cast<char*>(workspace);
+  float* G = reinterpret_cast<float*>(base + lay[0]);
+  float* stats = reinterpret_cast<float*>(base + lay[2]);
+  float* w = reinterpret_cast<float*>(base + lay[4]);
   hipStream_t s = as_stream(stream);
   const int tb = (B + LT - 1) / LT;
   hipLaunchKernelGGL(gram_kernel, dim3(tb, tb, T), dim3(256), 0, s, pooled_all, terms, G, B, R, D);

@@ -271,6 +271,7 @@ DEBUG_SIGNATURES = {
     "mca_dbg_plan_gemm_tn_group_det": (_I, [C.POINTER(_I64), C.POINTER(_I64), _I, _I64, _I, C.POINTER(TnGroupDetPlan)]),
     "mca_dbg_plan_layernorm_fwd": (_I, [C.POINTER(LnFwdProblem), C.POINTER(LnFwdPlan)]),
     "mca_dbg_plan_layernorm_bwd": (_I, [C.POINTER(LnBwdProblem), C.POINTER(LnBwdPlan)]),
+    "mca_dbg_contrastive_layout": (_I, [_I, _I, C.POINTER(_I64)]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -351,6 +352,13 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     if t is None:
         return None
     return t.data_ptr()
+
+
+def contrastive_layout(B: int, T: int) -> dict:
+    """{region: (byte offset, bytes)} of mca_contrastive_fwd_bwd's workspace for region in G, stats, w (include/mca_hip_debug.h)"""
+    out = (_I64 * 6)()
+    check(lib().mca_dbg_contrastive_layout(B, T, out), "mca_dbg_contrastive_layout")
+    return {"G": (out[0], out[1]), "stats": (out[2], out[3]), "w": (out[4], out[5])}
 
 
 def check(rc: int, what: str):

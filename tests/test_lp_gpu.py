@@ -11,6 +11,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from eval_edge_util import _mask_ref
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -126,20 +128,6 @@ def test_compute_cosines_and_cpu_inputs(mods):
     assert all(t.device.type == "cuda" and t.dim() == 0 for t in a)
     with pytest.raises(ValueError, match="cpu"):
         M.get_rank_metrics(x, mask, x, device="cpu")
-
-
-def _mask_ref(seed, step, rows, units, p):
-    """the kernel's dropout mask (csrc/evaluate.hip dropout_keep), restated: keep where a hash of (seed, step, row, unit) >= p"""
-    u64 = np.uint64
-
-    def fmix(k):
-        k = k ^ (k >> u64(33)); k = k * u64(0xff51afd7ed558ccd); k = k ^ (k >> u64(33))
-        k = k * u64(0xc4ceb9fe1a85ec53); return k ^ (k >> u64(33))
-    with np.errstate(over="ignore"):
-        r = np.arange(rows, dtype=np.uint64)[:, None]
-        u = np.arange(units, dtype=np.uint64)[None, :]
-        h = fmix(u64(seed) ^ fmix(u64(step) ^ fmix((r << u64(32)) | u)))
-    return torch.from_numpy((h >> u64(40)).astype(np.float32) * np.float32(2.0 ** -24) >= np.float32(p))
 
 
 def _loss(kind, z, y):
