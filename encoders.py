@@ -7,10 +7,10 @@ import importlib as _il
 _e = _il.import_module("mca-paper_amd.encoders")
 encoders_dict, collators, MultimodalCollator = _e.encoders_dict, _e.collators, _e.MultimodalCollator
 EmbeddedSequenceEncoder, TabularEncoder, PositionalEncoder = _e.EmbeddedSequenceEncoder, _e.TabularEncoder, _e.PositionalEncoder
-SequenceEncoder, SparseTabularEncoder = _e.SequenceEncoder, _e.SparseTabularEncoder
+SequenceEncoder, SparseTabularEncoder, PatchEncoder = _e.SequenceEncoder, _e.SparseTabularEncoder, _e.PatchEncoder
 TokenEncoder, ContinuousValueEncoder = _e._TokenTable, _e._ValueMLP
 SequenceCollator, EmbeddedSequenceCollator, MatrixCollator = _e.SequenceCollator, _e.EmbeddedSequenceCollator, _e.MatrixCollator
 
 __all__ = ["encoders_dict", "collators", "MultimodalCollator", "EmbeddedSequenceEncoder", "TabularEncoder", "PositionalEncoder",
-           "SequenceEncoder", "SparseTabularEncoder",
+           "SequenceEncoder", "SparseTabularEncoder", "PatchEncoder",
            "TokenEncoder", "ContinuousValueEncoder", "SequenceCollator", "EmbeddedSequenceCollator", "MatrixCollator"]

@@ -171,6 +171,24 @@ int mca_embedding_scatter_add(const float* dy, int64_t ldy, int64_t y_bstride, i
                               int64_t rows, float* dtable, int64_t vocab, int cols, int64_t padding_idx, mca_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PatchEncoder front end (encoders.py:247-251,260-262,273; mode "matrix"): patch gather + LayerNorm(P) + pad mask, one pass.
+ * --------------------------------------------------------------------------------------------- */
+/* Element (s, r, c) of values is at values + s*v_bstride + r*ldv + c.  Row t = s*n + i*(W/p2) + j, n = (H/p1)*(W/p2), is patch
+ * (i, j): its P = p1*p2 elements in (row-in-patch, column-in-patch) order.
+ *   xp[t*P ...]        the gathered patch, fp32 (what mca_layernorm_bwd reads as x in the backward); NULL to skip
+ *   xn_bf16[t*ld_bf16] bf16(LN(patch)*gamma + beta), zero-filled from P to cols_pad
+ *   mean[t], rstd[t]   the row's statistics
+ *   padmask[t]         1 if every element == pad_value (exact float compare; NaN is not equal), else 0
+ * A row with padmask 1 is written as its exact value: xn = bf16(beta), mean = pad_value, rstd = rsqrt(eps) (LayerNorm of a
+ * constant row multiplies any rounding of the mean by rsqrt(eps) = 316).
+ * Returns non-zero, launching nothing, for H % p1, W % p2, P > 1024, cols_pad < P, ld_bf16 < cols_pad, ldv < W or a NULL
+ * required pointer (every pointer but xp).                                                                               */
+int mca_patch_ln_fwd(const float* values, int64_t v_bstride, int64_t ldv, int batch, int H, int W, int p1, int p2,
+                     const float* gamma, const float* beta, float pad_value, float eps,
+                     float* xp, uint16_t* xn_bf16, int64_t ld_bf16, int cols_pad,
+                     float* mean, float* rstd, uint8_t* padmask, mca_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Block-masked fused attention (model.py:73-105 as used by MCALayer :119 and attn_pool :472-473)
  * --------------------------------------------------------------------------------------------- */
 /* Packing of the per-modality attention masks (model.py:455-466; encoders.py:196-214 for the row masks): ONE launch

@@ -8,6 +8,9 @@
                      ``attention_mask (b, n) int64`` = (tokens == 0); dropped modality = all-pad row.
   sparse tabular:    ``indices (b, n) int64`` as the token sequence's, ``data (b, n) f32`` in [1, 10), 0.0 where padded,
                      ``attention_mask (b, n) int64`` = (indices == 0).
+  patch (matrix):    ``values (b, H, W) f32`` (H, W = the config's ``input_shape``), rows past the valid row count -10000 as
+                     MatrixCollator pads them, a dropped modality all -10000; NO ``attention_mask``: the encoder derives it
+                     from the patches (a patch is padded when every element is -10000).
 """
 from __future__ import annotations
 
@@ -61,6 +64,18 @@ def synthetic_batch(model_config: dict, batch_size: int, seed: int = 1234, p_dro
             else:
                 vals = (torch.rand(batch_size, n, generator=g) * 9.0 + 1.0).masked_fill(pad, 0.0)
                 batch[name] = {"indices": idx.to(device), "data": vals.to(device), "attention_mask": mask.to(device)}
+        elif c["type"] == "PatchEncoder":
+            if "input_shape" not in c:
+                raise ValueError(f"synthetic_batch: PatchEncoder '{name}' needs the config key 'input_shape' ([H, W]) to draw a matrix")
+            H, W = c["input_shape"]
+            if lengths == "full":
+                ln = torch.full((batch_size,), H, dtype=torch.long)
+            else:
+                ln = torch.randint(1, H + 1, (batch_size,), generator=g)          # valid rows: a patch row may be cut through
+            ln = torch.where(drop[:, mi], torch.zeros_like(ln), ln)
+            pad = torch.arange(H)[None, :] >= ln[:, None]
+            vals = torch.randn(batch_size, H, W, generator=g).masked_fill(pad[..., None], -10000.0)
+            batch[name] = {"values": vals.to(device)}
         else:
             raise NotImplementedError(c["type"])
     return batch

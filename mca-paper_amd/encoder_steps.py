@@ -2,13 +2,13 @@
 its workspace buffers, the shapes of its deterministic launches, its forward and its backward.  The engine builds one per modality
 (step_for, the only place that looks at an encoder's type) and loops over them: a new encoder kind is a class here and a line in
 step_for.  Reference lines: encoders.py:196-214 (EmbeddedSequenceEncoder), :90-96 (TabularEncoder), :161-166 (SequenceEncoder), :114-120
-(SparseTabularEncoder).
+(SparseTabularEncoder), :260-273 (PatchEncoder).
 This module binds its own `call` from .hip: a tool that records launches by rebinding `call` patches hip, engine AND this module."""
 from __future__ import annotations
 
 import torch
 
-from .encoders import EmbeddedSequenceEncoder, SequenceEncoder, SparseTabularEncoder, TabularEncoder
+from .encoders import EmbeddedSequenceEncoder, PatchEncoder, SequenceEncoder, SparseTabularEncoder, TabularEncoder
 from .hip import call, ptr, stream_ptr
 
 FLAG_INDEX_RANGE = 4          # the engine's flag word: bit 1 non-finite encoder input, bit 2 non-finite output, this one a token index outside its table
@@ -22,6 +22,10 @@ class _Step:
 
     def _bf16(self, *shape):
         return torch.zeros(*shape, dtype=torch.bfloat16, device=self.eng.device)
+
+    def attention_mask(self, bm, ws):
+        """the (b, n) key-padding mask of the modality, non-zero = padded, which mca_pack_masks packs: the batch's own"""
+        return bm["attention_mask"]
 
 
 class SequenceStep(_Step):
@@ -243,6 +247,79 @@ class SparseTabularStep(_ValueChain, _TableLookup):
         self._value_backward(ws, dx, on_side)
 
 
+class PatchStep(_Step):
+    """PatchEncoder: `mca_patch_ln_fwd` (patch gather, LayerNorm(P), bf16 out, pad mask: launched by attention_mask(), before the
+    masks are packed) -> `mca_gemm_nt` + bias -> `mca_layernorm_fwd` (+ the learned position table, written into the packed token
+    matrix).  Padded tokens are not zeroed (encoders.py:268-274): no LayerNorm here takes a row mask."""
+    native = True
+
+    def __init__(self, engine, name, mi, enc):
+        super().__init__(engine, name, mi, enc)
+        self.p1, self.p2 = int(enc.patch_size[0]), int(enc.patch_size[1])
+        self.P = self.p1 * self.p2
+        self.kp = (self.P + 63) // 64 * 64          # the Linear's input width, padded to 64
+        self.w, self.wT = self._bf16(self.D, self.kp), self._bf16(self.kp, self.D)
+
+    def casts(self):
+        self.eng._cast(self.enc.batch_to_tokens[2].weight.data, self.w)
+        self.eng._cast(self.enc.batch_to_tokens[2].weight.data, self.wT, transpose=True)
+
+    def workspace(self, b, f32, bf, u8):
+        rows, D, kp = b * self.n, self.D, self.kp
+        return dict(xp=f32(rows, self.P), xin_b=bf(rows, kp), m0=f32(rows), r0=f32(rows), y=f32(rows, D), m2=f32(rows), r2=f32(rows),
+                    dy=f32(rows, D), dy_b=bf(rows, D), dxin=f32(rows, kp), mask=u8(rows))
+
+    def row_mask(self, ws):
+        return None          # (its mask comes from the values: mca_patch_ln_fwd)
+
+    def attention_mask(self, bm, ws):
+        """checks `values`, runs the front-end kernel and returns the mask it wrote, (b, n) uint8"""
+        from .engine import LN_EPS          # (here: engine imports this module)
+        n, b, p1, p2 = self.n, ws["b"], self.p1, self.p2
+        e, bt = ws["enc"][self.name], self.enc.batch_to_tokens
+        vals = bm["values"]
+        if vals.dtype != torch.float32 or not vals.is_contiguous():
+            vals = vals.float().contiguous()
+        if vals.dim() != 3 or vals.shape[0] != b:
+            raise AssertionError(f"{self.name}: values {tuple(vals.shape)} is not (b = {b}, H, W)")
+        H, W = vals.shape[1], vals.shape[2]
+        if H % p1 or W % p2:
+            raise AssertionError(f"{self.name}: values {tuple(vals.shape)} is not a whole number of {(p1, p2)} patches")
+        grid = (H // p1) * (W // p2)
+        if grid != n:
+            raise AssertionError(f"{grid} - {n}")                  # encoders.py:270
+        e["values"] = vals
+        call("mca_patch_ln_fwd", ptr(vals), H * W, W, b, H, W, p1, p2, ptr(bt[1].weight.data), ptr(bt[1].bias.data),
+             float(self.enc.pad_token), LN_EPS, ptr(e["xp"]), ptr(e["xin_b"]), self.kp, self.kp, ptr(e["m0"]), ptr(e["r0"]),
+             ptr(e["mask"]), stream_ptr())
+        return e["mask"].view(b, n)
+
+    def forward(self, bm, ws, need_grad):
+        eng, n, D, rows = self.eng, self.n, self.D, ws["b"] * self.n
+        e, bt = ws["enc"][self.name], self.enc.batch_to_tokens
+        eng.gemm_nt(e["xin_b"], self.w, e["y"], rows, D, self.kp, bias=bt[2].bias)
+        eng.ln_fwd(e["y"], bt[3].weight, rows, D, e["m2"], e["r2"], beta=bt[3].bias, add=self.enc.embedding.weight.data, period=n,
+                   y=ws["x"][0][self.off:], ldy=D, y_bstride=self.N * D)
+
+    def det_shapes(self, b):
+        """the deterministic launches of backward(): two LayerNorm backwards, one weight gradient, the position table's row sum"""
+        rows = b * self.n
+        return dict(ln=[(rows, self.D), (rows, self.P)], tn=[(rows, self.D, self.P)], rr=[(rows, self.n)])
+
+    def backward(self, ws, dx, on_side):
+        eng, n, off, D, N, G, P, kp = self.eng, self.n, self.off, self.D, self.N, self.G, self.P, self.kp
+        e, bt, rows = ws["enc"][self.name], self.enc.batch_to_tokens, ws["b"] * n
+        # the table is added to every row, padded or not: every row of dx reaches it (no frozen row: no padding_idx)
+        eng._reduce_rows(ws, dx.data_ptr() + off * D * 4, D, N * D, n, ptr(G(self.enc.embedding.weight)), D, rows, D)
+        # (the Linear's bias gradient = column sums of this norm's dx: same launch)
+        eng._ln_bwd(ws, dx[off:], D, e["y"], bt[3].weight, e["m2"], e["r2"], rows, D, G(bt[3].weight), dbeta=G(bt[3].bias),
+                    dx=e["dy"], dx_bf16=e["dy_b"], y_bstride=N * D, period=n, dxsum=G(bt[2].bias))
+        on_side(lambda e=e, bt=bt, rows=rows: eng._tn(ws, e["dy_b"], e["xin_b"], G(bt[2].weight), rows, D, P))
+        eng.gemm_nt(e["dy_b"], self.wT, e["dxin"], rows, kp, D)
+        # parameters only: the matrix needs no gradient
+        eng._ln_bwd(ws, e["dxin"], kp, e["xp"], bt[1].weight, e["m0"], e["r0"], rows, P, G(bt[1].weight), dbeta=G(bt[1].bias))
+
+
 class ForeignStep(_Step):
     """A user-registered torch encoder: it runs under autograd and feeds its tokens to the native trunk.  No bf16 copies, no
     workspace buffers, no deterministic launches (torch's own backward is not held to bit-equality)."""
@@ -282,4 +359,6 @@ def step_for(engine, name, mi, enc):
         return TokenSequenceStep(engine, name, mi, enc)
     if isinstance(enc, SparseTabularEncoder):
         return SparseTabularStep(engine, name, mi, enc)
+    if isinstance(enc, PatchEncoder):
+        return PatchStep(engine, name, mi, enc)
     return ForeignStep(engine, name, mi, enc)

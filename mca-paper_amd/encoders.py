@@ -125,11 +125,70 @@ class SparseTabularEncoder(NativeEncoder):
         self.value_encoder = _ValueMLP(embedding_dim, dropout, max_value, padding_idx)
 
 
+class _PatchRearrange(nn.Module):
+    """Parameter-less stand-in for the reference's ``Rearrange('b (h p1) (w p2) -> b (h w) (p1 p2)')`` at index 0 of
+    ``batch_to_tokens``: it keeps the state_dict keys of the layers after it (``batch_to_tokens.1`` ...) where the reference has
+    them.  The rearrangement itself is the gather of ``mca_patch_ln_fwd``."""
+
+    def __init__(self, p1, p2):
+        super().__init__()
+        self.p1, self.p2 = p1, p2
+
+
+class PatchEncoder(NativeEncoder):
+    """2-D matrix (a spectrogram) cut into (p1, p2) patches: ``batch["values"]`` (b, H, W) -> token t = i * (W / p2) + j is patch
+    (i, j), its P = p1 * p2 elements in (row, column) order; LN(P) -> Linear(P, D) -> LN(D) + a learned (max_tokens, D) position
+    table looked up by ``arange``.  ``attention_mask[s, t]`` = every element of the patch equals ``pad_token`` (-10000 whatever
+    the argument says, as the reference overwrites it); padded tokens are NOT zeroed (encoders.py:217-274).
+
+    Refused at construction (docs/scope_and_gaps.md): mode "image" / "video" (the reference's own forward cannot run them),
+    ``attn_mask=False`` (MCA.forward compares the returned None with 0), ``dropout != 0`` (the native step has no dropout) and
+    patches of more than 1024 elements (the kernel's limit).  Optional ``input_shape: [H, W]``, which the reference swallows in
+    ``**kwargs``, is checked against ``patch_size`` and ``max_tokens``."""
+    kind = "patch"
+
+    def __init__(self, patch_size=(16, 16), mode="matrix", num_channels=0, embedding_dim=512, max_tokens=1024, dropout: float = 0.1,
+                 attn_mask=True, pad_token=-10000, input_shape=None, **kwargs):
+        super().__init__()
+        assert mode in ["matrix", "image", "video"]                                                                  # encoders.py:242
+        if mode != "matrix":
+            raise NotImplementedError(f"PatchEncoder: mode '{mode}' is not supported: the reference's forward can only run mode "
+                                      "'matrix' (its mask layer exists for that mode alone and its other rearrangements do not "
+                                      "yield (b, l, D) tokens)")
+        assert len(patch_size) == 2                                                                                  # encoders.py:244
+        if not attn_mask:
+            raise NotImplementedError("PatchEncoder: attn_mask=False is not supported: the encoder would return None as its mask, "
+                                      "which MCA.forward compares with 0")
+        if dropout != 0.0:
+            raise NotImplementedError(f"PatchEncoder: dropout={dropout} is not supported: the native step has no dropout; pass "
+                                      "'dropout: 0.0' in the encoder's config")
+        p1, p2 = int(patch_size[0]), int(patch_size[1])
+        if p1 < 1 or p2 < 1 or p1 * p2 > 1024:
+            raise NotImplementedError(f"PatchEncoder: patch_size {tuple(patch_size)} has {p1 * p2} elements; the native kernel takes "
+                                      "1 to 1024 (32 x 32)")
+        if input_shape is not None:
+            H, W = int(input_shape[0]), int(input_shape[1])
+            if H % p1 or W % p2 or (H // p1) * (W // p2) != max_tokens:
+                raise ValueError(f"PatchEncoder: input_shape {(H, W)} in patches of {(p1, p2)} does not give max_tokens = {max_tokens} "
+                                 "whole patches")
+        self.attn_mask = attn_mask
+        self.pad_token = -10000                                                                                      # encoders.py:239
+        self.patch_size = patch_size
+        self.embedding_dim = embedding_dim
+        self.max_tokens = max_tokens
+        self.input_shape = None if input_shape is None else (int(input_shape[0]), int(input_shape[1]))
+        self.batch_to_tokens = nn.Sequential(_PatchRearrange(p1, p2), nn.LayerNorm(p1 * p2), nn.Linear(p1 * p2, embedding_dim),
+                                             nn.LayerNorm(embedding_dim))
+        self.register_buffer("index", torch.arange(max_tokens))
+        self.embedding = nn.Embedding(max_tokens, embedding_dim)
+
+
 encoders_dict: Dict[str, type] = {
     "EmbeddedSequenceEncoder": EmbeddedSequenceEncoder,
     "TabularEncoder": TabularEncoder,
     "SequenceEncoder": SequenceEncoder,
     "SparseTabularEncoder": SparseTabularEncoder,
+    "PatchEncoder": PatchEncoder,
 }
 
 

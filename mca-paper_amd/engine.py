@@ -595,7 +595,7 @@ class FusionEngine:
             if not step.native:
                 continue
             name, mi, n, off = step.name, step.mi, step.n, step.off
-            am = batch[name]["attention_mask"]
+            am = step.attention_mask(batch[name], ws)
             if am.dtype == torch.bool or am.dtype == torch.uint8:
                 eb = 1
             elif am.dtype == torch.int64:

@@ -213,6 +213,7 @@ SIGNATURES = {
     "mca_embedding_scatter_add": (_I, [_P, _I64, _I64, _I64, _P, _I, _I64, _P, _I64, _I, _I64, _P]),
     "mca_tab_value_fwd": (_I, [_P, _P, _P, _P, _P, _I64, _I, _F, _F, _P]),
     "mca_tab_value_bwd": (_I, [_P, _I64, _P, _P, _P, _P, _I64, _I, _F, _P]),
+    "mca_patch_ln_fwd": (_I, [_P, _I64, _I64, _I, _I, _I, _I, _I, _P, _P, _F, _F, _P, _P, _I64, _I, _P, _P, _P, _P]),
     "mca_pack_masks": (_I, [_P, _P, _P, _P]),
     "mca_build_keyinfo": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "mca_attn_vmean": (_I, [_P, _I64, _I64, _P, _I, _I, _I, _P]),
