@@ -9,8 +9,11 @@ encoders_dict, collators, MultimodalCollator = _e.encoders_dict, _e.collators, _
 EmbeddedSequenceEncoder, TabularEncoder, PositionalEncoder = _e.EmbeddedSequenceEncoder, _e.TabularEncoder, _e.PositionalEncoder
 SequenceEncoder, SparseTabularEncoder, PatchEncoder = _e.SequenceEncoder, _e.SparseTabularEncoder, _e.PatchEncoder
 TokenEncoder, ContinuousValueEncoder = _e._TokenTable, _e._ValueMLP
+ImagePatchEncoder, VideoPatchEncoder = _e.ImagePatchEncoder, _e.VideoPatchEncoder
 SequenceCollator, EmbeddedSequenceCollator, MatrixCollator = _e.SequenceCollator, _e.EmbeddedSequenceCollator, _e.MatrixCollator
+ImageCollator, VideoCollator = _e.ImageCollator, _e.VideoCollator
 
 __all__ = ["encoders_dict", "collators", "MultimodalCollator", "EmbeddedSequenceEncoder", "TabularEncoder", "PositionalEncoder",
-           "SequenceEncoder", "SparseTabularEncoder", "PatchEncoder",
-           "TokenEncoder", "ContinuousValueEncoder", "SequenceCollator", "EmbeddedSequenceCollator", "MatrixCollator"]
+           "SequenceEncoder", "SparseTabularEncoder", "PatchEncoder", "ImagePatchEncoder", "VideoPatchEncoder",
+           "TokenEncoder", "ContinuousValueEncoder", "SequenceCollator", "EmbeddedSequenceCollator", "MatrixCollator",
+           "ImageCollator", "VideoCollator"]

@@ -188,6 +188,21 @@ int mca_patch_ln_fwd(const float* values, int64_t v_bstride, int64_t ldv, int ba
                      float* xp, uint16_t* xn_bf16, int64_t ld_bf16, int cols_pad,
                      float* mean, float* rstd, uint8_t* padmask, mca_stream_t stream);
 
+/* The same pass over a (b, C, T, H, W) batch cut into (pt, p1, p2) patches (ImagePatchEncoder: T = pt = 1; VideoPatchEncoder).
+ * Element (s, c, t, r, w) of values is at values + s*v_bstride + c*v_cstride + t*v_fstride + r*ldv + w, so planes and frames may
+ * be framed apart.  With gt = T/pt, gh = H/p1, gw = W/p2, row ((s*gt + ti)*gh + hi)*gw + wi is patch (ti, hi, wi) of sample s, and
+ * its element ((c*pt + dt)*p1 + r)*p2 + col is values[s, c, ti*pt + dt, hi*p1 + r, wi*p2 + col]; P = C*pt*p1*p2.
+ * Outputs and all-pad semantics as mca_patch_ln_fwd: a row has padmask 1 only when every element of every channel and frame of
+ * the patch == pad_value.  With C = T = pt = 1 the outputs equal mca_patch_ln_fwd's bit for bit.
+ * Returns non-zero, launching nothing, for T % pt, H % p1, W % p2, P > 1024, cols_pad < P, ld_bf16 < cols_pad, ldv < W, a frame
+ * stride (T > 1) below (H-1)*ldv + W, a channel stride (C > 1) below (T-1)*v_fstride + (H-1)*ldv + W, a batch stride (batch > 1)
+ * below (C-1)*v_cstride + that, or a NULL required pointer (every pointer but xp).                                              */
+int mca_patch_nd_ln_fwd(const float* values, int64_t v_bstride, int64_t v_cstride, int64_t v_fstride, int64_t ldv,
+                        int batch, int C, int T, int H, int W, int pt, int p1, int p2,
+                        const float* gamma, const float* beta, float pad_value, float eps,
+                        float* xp, uint16_t* xn_bf16, int64_t ld_bf16, int cols_pad,
+                        float* mean, float* rstd, uint8_t* padmask, mca_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Block-masked fused attention (model.py:73-105 as used by MCALayer :119 and attn_pool :472-473)
  * --------------------------------------------------------------------------------------------- */

@@ -24,7 +24,8 @@ extern "C" {
  *       register staging instead of LDS-DMA
  *   12  = 1: general LayerNorm kernels where the trunk forms would be chosen
  *   13  mca_patch_ln_fwd: +c = at most c patches per workgroup; -c = the same cap in the wavefront-per-patch form that reads
- *       each patch from global memory instead of staging strip rows through LDS (same results; profiles/patch_encoder.md)
+ *       each patch from global memory instead of staging strip rows through LDS (same results; profiles/patch_encoder.md).
+ *       mca_patch_nd_ln_fwd: |c| caps the span the same way; it has no wavefront-per-patch form, the sign is ignored
  *   14  > 0: cap on the workgroups of the LayerNorm backward kernels (default 256) and of mca_reduce_rows (default 512)
  *   (13, in its earlier use, and 15 selected / tuned the forward attention forms of round 4; gone with tools/overlays/fwd64)
  *   one-pass attention backward (attention_bwd1.hip), knob 9: 8 = s_memtime stamps (trace build, tools/trace_bwd1.py), 16 = launch

@@ -11,6 +11,9 @@
   patch (matrix):    ``values (b, H, W) f32`` (H, W = the config's ``input_shape``), rows past the valid row count -10000 as
                      MatrixCollator pads them, a dropped modality all -10000; NO ``attention_mask``: the encoder derives it
                      from the patches (a patch is padded when every element is -10000).
+  image / video patch: ``values (b, C, H, W) f32`` / ``(b, C, T, H, W) f32`` (the config's ``num_channels`` and ``input_shape``),
+                     an image's rows / a clip's frames past the valid count -10000 in every channel, a dropped modality all
+                     -10000; no ``attention_mask`` either.
 """
 from __future__ import annotations
 
@@ -75,6 +78,21 @@ def synthetic_batch(model_config: dict, batch_size: int, seed: int = 1234, p_dro
             ln = torch.where(drop[:, mi], torch.zeros_like(ln), ln)
             pad = torch.arange(H)[None, :] >= ln[:, None]
             vals = torch.randn(batch_size, H, W, generator=g).masked_fill(pad[..., None], -10000.0)
+            batch[name] = {"values": vals.to(device)}
+        elif c["type"] in ("ImagePatchEncoder", "VideoPatchEncoder"):
+            nd = 2 if c["type"] == "ImagePatchEncoder" else 3
+            if len(c.get("input_shape") or ()) != nd:
+                raise ValueError(f"synthetic_batch: {c['type']} '{name}' needs the config key 'input_shape' "
+                                 f"({'[H, W]' if nd == 2 else '[T, H, W]'}) to draw a sample")
+            shape = (c["num_channels"], *c["input_shape"])
+            L = shape[1]                                              # an image's rows, a clip's frames: the axis a random tail of is padded
+            if lengths == "full":
+                ln = torch.full((batch_size,), L, dtype=torch.long)
+            else:
+                ln = torch.randint(1, L + 1, (batch_size,), generator=g)          # a patch may be cut through
+            ln = torch.where(drop[:, mi], torch.zeros_like(ln), ln)
+            pad = (torch.arange(L)[None, :] >= ln[:, None]).view(batch_size, 1, L, *([1] * (nd - 1)))
+            vals = torch.randn(batch_size, *shape, generator=g).masked_fill(pad, -10000.0)
             batch[name] = {"values": vals.to(device)}
         else:
             raise NotImplementedError(c["type"])

@@ -2,13 +2,13 @@
 its workspace buffers, the shapes of its deterministic launches, its forward and its backward.  The engine builds one per modality
 (step_for, the only place that looks at an encoder's type) and loops over them: a new encoder kind is a class here and a line in
 step_for.  Reference lines: encoders.py:196-214 (EmbeddedSequenceEncoder), :90-96 (TabularEncoder), :161-166 (SequenceEncoder), :114-120
-(SparseTabularEncoder), :260-273 (PatchEncoder).
+(SparseTabularEncoder), :260-273 (PatchEncoder; its modes "image" and "video": ImagePatchEncoder, VideoPatchEncoder).
 This module binds its own `call` from .hip: a tool that records launches by rebinding `call` patches hip, engine AND this module."""
 from __future__ import annotations
 
 import torch
 
-from .encoders import EmbeddedSequenceEncoder, PatchEncoder, SequenceEncoder, SparseTabularEncoder, TabularEncoder
+from .encoders import EmbeddedSequenceEncoder, ImagePatchEncoder, PatchEncoder, SequenceEncoder, SparseTabularEncoder, TabularEncoder, VideoPatchEncoder
 from .hip import call, ptr, stream_ptr
 
 FLAG_INDEX_RANGE = 4          # the engine's flag word: bit 1 non-finite encoder input, bit 2 non-finite output, this one a token index outside its table
@@ -255,10 +255,13 @@ class PatchStep(_Step):
 
     def __init__(self, engine, name, mi, enc):
         super().__init__(engine, name, mi, enc)
-        self.p1, self.p2 = int(enc.patch_size[0]), int(enc.patch_size[1])
-        self.P = self.p1 * self.p2
+        self.P = self._patch_elements(enc)
         self.kp = (self.P + 63) // 64 * 64          # the Linear's input width, padded to 64
         self.w, self.wT = self._bf16(self.D, self.kp), self._bf16(self.kp, self.D)
+
+    def _patch_elements(self, enc):
+        self.p1, self.p2 = int(enc.patch_size[0]), int(enc.patch_size[1])
+        return self.p1 * self.p2
 
     def casts(self):
         self.eng._cast(self.enc.batch_to_tokens[2].weight.data, self.w)
@@ -320,6 +323,38 @@ class PatchStep(_Step):
         eng._ln_bwd(ws, e["dxin"], kp, e["xp"], bt[1].weight, e["m0"], e["r0"], rows, P, G(bt[1].weight), dbeta=G(bt[1].bias))
 
 
+class PatchNDStep(PatchStep):
+    """ImagePatchEncoder / VideoPatchEncoder: PatchStep with `mca_patch_nd_ln_fwd` as its front end: values (b, C, H, W) or
+    (b, C, T, H, W), P = C * pt * p1 * p2 (an image has pt = T = 1).  Everything behind the gather - workspace, forward, backward,
+    deterministic launches - is PatchStep's."""
+
+    def _patch_elements(self, enc):
+        self.C, (self.pt, self.p1, self.p2) = enc.num_channels, enc.patch
+        return self.C * self.pt * self.p1 * self.p2
+
+    def attention_mask(self, bm, ws):
+        """checks `values`, runs the front-end kernel and returns the mask it wrote, (b, n) uint8"""
+        from .engine import LN_EPS          # (here: engine imports this module)
+        n, b, C, pt, p1, p2 = self.n, ws["b"], self.C, self.pt, self.p1, self.p2
+        e, bt, image = ws["enc"][self.name], self.enc.batch_to_tokens, self.enc.ndim == 2
+        vals = bm["values"]
+        if vals.dtype != torch.float32 or not vals.is_contiguous():
+            vals = vals.float().contiguous()
+        if vals.dim() != (4 if image else 5) or vals.shape[0] != b or vals.shape[1] != C:
+            raise AssertionError(f"{self.name}: values {tuple(vals.shape)} is not (b = {b}, C = {C}, {'H, W' if image else 'T, H, W'})")
+        T, H, W = (1, *vals.shape[2:]) if image else vals.shape[2:]
+        if T % pt or H % p1 or W % p2:
+            raise AssertionError(f"{self.name}: values {tuple(vals.shape)} is not a whole number of {tuple(self.enc.patch_size)} patches")
+        grid = (T // pt) * (H // p1) * (W // p2)
+        if grid != n:
+            raise AssertionError(f"{grid} - {n}")                  # encoders.py:270
+        e["values"] = vals
+        call("mca_patch_nd_ln_fwd", ptr(vals), C * T * H * W, T * H * W, H * W, W, b, C, T, H, W, pt, p1, p2, ptr(bt[1].weight.data),
+             ptr(bt[1].bias.data), float(self.enc.pad_token), LN_EPS, ptr(e["xp"]), ptr(e["xin_b"]), self.kp, self.kp, ptr(e["m0"]),
+             ptr(e["r0"]), ptr(e["mask"]), stream_ptr())
+        return e["mask"].view(b, n)
+
+
 class ForeignStep(_Step):
     """A user-registered torch encoder: it runs under autograd and feeds its tokens to the native trunk.  No bf16 copies, no
     workspace buffers, no deterministic launches (torch's own backward is not held to bit-equality)."""
@@ -361,4 +396,6 @@ def step_for(engine, name, mi, enc):
         return SparseTabularStep(engine, name, mi, enc)
     if isinstance(enc, PatchEncoder):
         return PatchStep(engine, name, mi, enc)
+    if isinstance(enc, (ImagePatchEncoder, VideoPatchEncoder)):
+        return PatchNDStep(engine, name, mi, enc)
     return ForeignStep(engine, name, mi, enc)

@@ -128,7 +128,7 @@ class SparseTabularEncoder(NativeEncoder):
 class _PatchRearrange(nn.Module):
     """Parameter-less stand-in for the reference's ``Rearrange('b (h p1) (w p2) -> b (h w) (p1 p2)')`` at index 0 of
     ``batch_to_tokens``: it keeps the state_dict keys of the layers after it (``batch_to_tokens.1`` ...) where the reference has
-    them.  The rearrangement itself is the gather of ``mca_patch_ln_fwd``."""
+    them.  The rearrangement itself is the gather of ``mca_patch_ln_fwd`` (``mca_patch_nd_ln_fwd`` for images and video)."""
 
     def __init__(self, p1, p2):
         super().__init__()
@@ -144,7 +144,8 @@ class PatchEncoder(NativeEncoder):
     Refused at construction (docs/scope_and_gaps.md): mode "image" / "video" (the reference's own forward cannot run them),
     ``attn_mask=False`` (MCA.forward compares the returned None with 0), ``dropout != 0`` (the native step has no dropout) and
     patches of more than 1024 elements (the kernel's limit).  Optional ``input_shape: [H, W]``, which the reference swallows in
-    ``**kwargs``, is checked against ``patch_size`` and ``max_tokens``."""
+    ``**kwargs``, is checked against ``patch_size`` and ``max_tokens``.  Images and video clips: ImagePatchEncoder,
+    VideoPatchEncoder."""
     kind = "patch"
 
     def __init__(self, patch_size=(16, 16), mode="matrix", num_channels=0, embedding_dim=512, max_tokens=1024, dropout: float = 0.1,
@@ -183,12 +184,90 @@ class PatchEncoder(NativeEncoder):
         self.embedding = nn.Embedding(max_tokens, embedding_dim)
 
 
+class _PatchNDEncoder(NativeEncoder):
+    """What ImagePatchEncoder and VideoPatchEncoder share: the reference's PatchEncoder constructor in mode "image" / "video"
+    (encoders.py:226-267: same keywords, module tree, state_dict keys and RNG order) with the one repair that yields (b, l, D)
+    tokens: the patch grid axes are merged.  ``patch`` is (pt, p1, p2) and ``input_shape`` (T, H, W), an image having pt = T = 1."""
+    ndim = 0
+
+    def __init__(self, patch_size, num_channels=0, embedding_dim=512, max_tokens=1024, dropout: float = 0.1, attn_mask=True,
+                 pad_token=-10000, input_shape=None, **kwargs):
+        super().__init__()
+        name = type(self).__name__
+        assert len(patch_size) == self.ndim                                                                      # encoders.py:243-246
+        C = int(num_channels)
+        if C < 1:
+            raise ValueError(f"{name}: num_channels = {num_channels}: pass the number of channels of the input (the reference's "
+                             "default 0 gives a Linear of zero width)")
+        if not attn_mask:
+            raise NotImplementedError(f"{name}: attn_mask=False is not supported: the encoder would return None as its mask, "
+                                      "which MCA.forward compares with 0")
+        if dropout != 0.0:
+            raise NotImplementedError(f"{name}: dropout={dropout} is not supported: the native step has no dropout; pass "
+                                      "'dropout: 0.0' in the encoder's config")
+        patch = (1,) * (3 - self.ndim) + tuple(int(p) for p in patch_size)
+        P = C * patch[0] * patch[1] * patch[2]
+        if min(patch) < 1 or P > 1024:
+            raise NotImplementedError(f"{name}: patch_size {tuple(patch_size)} over {C} channels has {P} elements; the native "
+                                      "kernel takes 1 to 1024")
+        if input_shape is not None:
+            if len(input_shape) != self.ndim:
+                raise ValueError(f"{name}: input_shape {tuple(input_shape)} does not have {self.ndim} entries")
+            shape = (1,) * (3 - self.ndim) + tuple(int(x) for x in input_shape)
+            grid = [x // p for x, p in zip(shape, patch)]
+            if any(x % p for x, p in zip(shape, patch)) or grid[0] * grid[1] * grid[2] != max_tokens:
+                raise ValueError(f"{name}: input_shape {tuple(input_shape)} in patches of {tuple(patch_size)} does not give "
+                                 f"max_tokens = {max_tokens} whole patches")
+            self.input_shape = tuple(int(x) for x in input_shape)
+        else:
+            self.input_shape = None
+        self.attn_mask = attn_mask
+        self.pad_token = -10000                                                                                  # encoders.py:239
+        self.patch_size = patch_size
+        self.patch = patch
+        self.num_channels = C
+        self.embedding_dim = embedding_dim
+        self.max_tokens = max_tokens
+        self.batch_to_tokens = nn.Sequential(_PatchRearrange(*patch[1:]), nn.LayerNorm(P), nn.Linear(P, embedding_dim),
+                                             nn.LayerNorm(embedding_dim))
+        self.register_buffer("index", torch.arange(max_tokens))
+        self.embedding = nn.Embedding(max_tokens, embedding_dim)
+
+
+class ImagePatchEncoder(_PatchNDEncoder):
+    """Image (b, C, H, W) cut into (p1, p2) patches, 'b c (h p1) (w p2) -> b (h w) (c p1 p2)': token t = hi * (W / p2) + wi, its
+    P = C * p1 * p2 elements in (channel, row, column) order; then as PatchEncoder: LN(P) -> Linear(P, D) -> LN(D) + the learned
+    position table.  ``attention_mask[s, t]`` = every element of every channel of the patch equals ``pad_token`` (-10000).
+    Refused at construction (docs/scope_and_gaps.md): ``num_channels < 1``, ``attn_mask=False``, ``dropout != 0``, more than
+    1024 elements per patch, an ``input_shape: [H, W]`` that does not give ``max_tokens`` whole patches."""
+    kind = "image_patch"
+    ndim = 2
+
+    def __init__(self, patch_size=(16, 16), num_channels=0, embedding_dim=512, max_tokens=1024, dropout: float = 0.1, attn_mask=True,
+                 pad_token=-10000, input_shape=None, **kwargs):
+        super().__init__(patch_size, num_channels, embedding_dim, max_tokens, dropout, attn_mask, pad_token, input_shape, **kwargs)
+
+
+class VideoPatchEncoder(_PatchNDEncoder):
+    """Video clip (b, C, T, H, W) cut into (pt, p1, p2) tubelets, 'b c (t p1) (h p2) (w p3) -> b (t h w) (c p1 p2 p3)': token
+    (ti * (H / p1) + hi) * (W / p2) + wi, its P = C * pt * p1 * p2 elements in (channel, frame, row, column) order; otherwise as
+    ImagePatchEncoder, with ``input_shape: [T, H, W]``."""
+    kind = "video_patch"
+    ndim = 3
+
+    def __init__(self, patch_size=(2, 16, 16), num_channels=0, embedding_dim=512, max_tokens=1024, dropout: float = 0.1,
+                 attn_mask=True, pad_token=-10000, input_shape=None, **kwargs):
+        super().__init__(patch_size, num_channels, embedding_dim, max_tokens, dropout, attn_mask, pad_token, input_shape, **kwargs)
+
+
 encoders_dict: Dict[str, type] = {
     "EmbeddedSequenceEncoder": EmbeddedSequenceEncoder,
     "TabularEncoder": TabularEncoder,
     "SequenceEncoder": SequenceEncoder,
     "SparseTabularEncoder": SparseTabularEncoder,
     "PatchEncoder": PatchEncoder,
+    "ImagePatchEncoder": ImagePatchEncoder,
+    "VideoPatchEncoder": VideoPatchEncoder,
 }
 
 
@@ -292,10 +371,54 @@ class MatrixCollator:
         return {"values": torch.stack(outs)}
 
 
+class PatchNDCollator:
+    """Images (C, H, W) (type "image", ``input_shape: [H, W]``) or video clips (C, T, H, W) (type "video", ``input_shape:
+    [T, H, W]``) of ``num_channels`` channels stacked into ``values`` (b, C, H, W) / (b, C, T, H, W) float32; no
+    ``attention_mask``: the encoder derives it from the patches.  A missing sample (None) is a block of ``pad_token``.  A clip
+    with fewer than T frames is padded at the end with ``pad_token`` (its wholly missing temporal patches come out masked), a
+    longer one is cropped; any other shape mismatch is an error.  One output buffer is filled in place."""
+    ndim = 0
+
+    def __init__(self, num_channels, input_shape, pad_token=-10000, **kwargs):
+        if len(input_shape) != self.ndim:
+            raise ValueError(f"{type(self).__name__}: input_shape {tuple(input_shape)} does not have {self.ndim} entries")
+        self.pad_token = pad_token
+        self.shape = (int(num_channels),) + tuple(int(x) for x in input_shape)
+
+    def __call__(self, data):
+        samples = data["values"]
+        out = _batch_buffer((len(samples),) + self.shape, self.pad_token, torch.float32)
+        for i, x in enumerate(samples):
+            if x is None:
+                continue
+            want, got = self.shape, tuple(x.shape)
+            if self.ndim == 3 and len(got) == 4:          # the frame axis alone may differ
+                want, got = want[:1] + want[2:], got[:1] + got[2:]
+            if got != want:
+                raise ValueError(f"{type(self).__name__}: sample {i} has shape {tuple(x.shape)}; the modality's samples are "
+                                 f"{self.shape}" + (" (any number of frames)" if self.ndim == 3 else ""))
+            if self.ndim == 3:
+                t = min(x.shape[1], self.shape[1])
+                out[i, :, :t] = x[:, :t]
+            else:
+                out[i] = x
+        return {"values": out}
+
+
+class ImageCollator(PatchNDCollator):
+    ndim = 2
+
+
+class VideoCollator(PatchNDCollator):
+    ndim = 3
+
+
 collators: Dict[str, type] = {
     "matrix": MatrixCollator,
     "sequence": SequenceCollator,
     "embedded_sequence": EmbeddedSequenceCollator,
+    "image": ImageCollator,
+    "video": VideoCollator,
 }
 
 

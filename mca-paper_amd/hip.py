@@ -214,6 +214,7 @@ SIGNATURES = {
     "mca_tab_value_fwd": (_I, [_P, _P, _P, _P, _P, _I64, _I, _F, _F, _P]),
     "mca_tab_value_bwd": (_I, [_P, _I64, _P, _P, _P, _P, _I64, _I, _F, _P]),
     "mca_patch_ln_fwd": (_I, [_P, _I64, _I64, _I, _I, _I, _I, _I, _P, _P, _F, _F, _P, _P, _I64, _I, _P, _P, _P, _P]),
+    "mca_patch_nd_ln_fwd": (_I, [_P, _I64, _I64, _I64, _I64, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _P, _P, _I64, _I, _P, _P, _P, _P]),
     "mca_pack_masks": (_I, [_P, _P, _P, _P]),
     "mca_build_keyinfo": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "mca_attn_vmean": (_I, [_P, _I64, _I64, _P, _I, _I, _I, _P]),
