@@ -61,6 +61,20 @@ int mca_gemm_nt_geglu_bwd(const uint16_t* A, int64_t lda, const uint16_t* B, int
 int mca_gemm_nt_geglu_fwd(const uint16_t* A, int64_t lda, const uint16_t* W1, int64_t ldb, uint16_t* h, int64_t ldh,
                           uint16_t* g, int64_t ldg, int64_t ip, int64_t M, int64_t K, mca_stream_t stream);
 
+/* The saved-factor forms of the two fusions above: the forward keeps the two factors its backward multiplies by instead
+ * of h, in h's place (same shape [M, 2*ip], bf16, same strides):
+ *     s[:, 0:ip]    = bf16(gelu(gate_b))
+ *     s[:, ip:2*ip] = bf16(a_b * gelu'(gate_b))
+ * with a_b, gate_b the bf16-rounded halves of A·W1^T, i.e. exactly what the unsaved form stores as h; g is bit for bit
+ * the g of the unsaved form.  Where both halves of h are zero (the padded columns ip > I) both factors are zero.
+ * The backward is then dh[:, n] = bf16(dg * s[:, n]), dh[:, ip+n] = bf16(dg * s[:, ip+n]): no gelu is evaluated again,
+ * at one more bf16 rounding (2^-9 relative) per element of dh than the unsaved pair.  Arguments, their rules, the kernels'
+ * grids and the fall-backs are those of the siblings, s in the place of h; an s must only ever meet a _saved backward. */
+int mca_gemm_nt_geglu_fwd_saved(const uint16_t* A, int64_t lda, const uint16_t* W1, int64_t ldb, uint16_t* s, int64_t lds,
+                                uint16_t* g, int64_t ldg, int64_t ip, int64_t M, int64_t K, mca_stream_t stream);
+int mca_gemm_nt_geglu_bwd_saved(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const uint16_t* s,
+                                uint16_t* dh, int64_t ldh, int64_t ip, int64_t M, int64_t K, mca_stream_t stream);
+
 /* C[N,K] += A[R,N]^T · B[R,K]   (weight gradient: reduction over the R token rows; fp32 atomics
  * into C, which the caller zeroes once per step).  lda/ldb % 8 == 0; N and K are arbitrary but the
  * rows of A / B must be readable up to the next multiple of 8 columns (lda >= roundup8(N) etc.).  */
@@ -112,6 +126,12 @@ int mca_layernorm_bwd(const float* dy, int64_t ldy, int64_t y_bstride, int64_t p
 int mca_geglu_fwd(const uint16_t* h, uint16_t* g, int64_t rows, int ip, mca_stream_t stream);
 int mca_geglu_bwd(const uint16_t* dg, const uint16_t* h, uint16_t* dh, int64_t rows, int ip,
                   mca_stream_t stream);
+/* The stand-alone siblings of the saved-factor GEMM forms above (their fall-back for small or oddly shaped problems).
+ * Forward: s holds h = [a | gate] on entry and the factors [gelu(gate) | a * gelu'(gate)] on return, IN PLACE; g as the
+ * unsaved kernel writes it.  Backward: dh = [dg * s_lo | dg * s_hi].                                              */
+int mca_geglu_fwd_saved(uint16_t* s, uint16_t* g, int64_t rows, int ip, mca_stream_t stream);
+int mca_geglu_bwd_saved(const uint16_t* dg, const uint16_t* s, uint16_t* dh, int64_t rows, int ip,
+                        mca_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * small data-movement helpers

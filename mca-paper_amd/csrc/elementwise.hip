@@ -549,8 +549,12 @@ extern "C" int mca_dbg_plan_layernorm_bwd(const mca_ln_bwd_problem* pr, mca_ln_b
 
 // =====================================================================================================
 // GEGLU (model.py:35-38).  h = [a | gate], g = gelu_erf(gate) * a.  8 bf16 per lane per access.
+// SAVED (mca_geglu_fwd_saved / _bwd_saved): the forward overwrites h IN PLACE with the backward's two factors
+// s = [gelu_erf(gate) | a * gelu_erf'(gate)] (a lane reads its two pieces of h before it stores to them; h carries no
+// __restrict__ for that reason), and the backward only multiplies: dh = [dg * s_lo | dg * s_hi].
 // =====================================================================================================
-__global__ __launch_bounds__(256) void geglu_fwd_kernel(const u16* __restrict__ h, u16* __restrict__ g,
+template <bool SAVED>
+__global__ __launch_bounds__(256) void geglu_fwd_kernel(const u16* h, u16* __restrict__ g,
                                                          int64_t rows, int ip) {
   const int chunks = ip / 8;
   const int64_t total = rows * chunks;
@@ -559,13 +563,23 @@ __global__ __launch_bounds__(256) void geglu_fwd_kernel(const u16* __restrict__ 
     const int c = (int)(idx % chunks) * 8;
     const bf16x8 a = *reinterpret_cast<const bf16x8*>(h + r * 2 * ip + c);
     const bf16x8 gt = *reinterpret_cast<const bf16x8*>(h + r * 2 * ip + ip + c);
-    bf16x8 o;
+    bf16x8 o, slo, shi;
 #pragma unroll
-    for (int j = 0; j < 8; j++) o[j] = (short)f2bf(gelu_erf(bf2f((u16)gt[j])) * bf2f((u16)a[j]));
+    for (int j = 0; j < 8; j++) {
+      const float gv = bf2f((u16)gt[j]), av = bf2f((u16)a[j]), ge = gelu_erf(gv);
+      o[j] = (short)f2bf(ge * av);
+      if (SAVED) { slo[j] = (short)f2bf(ge); shi[j] = (short)f2bf(av * gelu_erf_grad(gv)); }
+    }
     *reinterpret_cast<bf16x8*>(g + r * ip + c) = o;
+    if (SAVED) {
+      u16* s = const_cast<u16*>(h);
+      *reinterpret_cast<bf16x8*>(s + r * 2 * ip + c) = slo;
+      *reinterpret_cast<bf16x8*>(s + r * 2 * ip + ip + c) = shi;
+    }
   }
 }
 
+template <bool SAVED>
 __global__ __launch_bounds__(256) void geglu_bwd_kernel(const u16* __restrict__ dg, const u16* __restrict__ h,
                                                          u16* __restrict__ dh, int64_t rows, int ip) {
   const int chunks = ip / 8;
@@ -580,6 +594,7 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(const u16* __restrict__ 
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       const float gv = bf2f((u16)gt[j]), av = bf2f((u16)a[j]), dv = bf2f((u16)d[j]);
+      if (SAVED) { da[j] = (short)f2bf(dv * av); dgt[j] = (short)f2bf(dv * gv); continue; }          // av = s_lo, gv = s_hi
       da[j] = (short)f2bf(dv * gelu_erf(gv));
       dgt[j] = (short)f2bf(dv * av * gelu_erf_grad(gv));
     }
@@ -598,14 +613,27 @@ static inline unsigned stream_grid(int64_t items) {
 extern "C" int mca_geglu_fwd(const uint16_t* h, uint16_t* g, int64_t rows, int ip, mca_stream_t stream) {
   if (!h || !g || rows < 0 || ip <= 0 || ip % 8) return MCA_E_BADARG;
   if (rows == 0) return MCA_OK;
-  hipLaunchKernelGGL(geglu_fwd_kernel, dim3(stream_grid(rows * (ip / 8))), dim3(256), 0, as_stream(stream), h, g, rows, ip);
+  hipLaunchKernelGGL(geglu_fwd_kernel<false>, dim3(stream_grid(rows * (ip / 8))), dim3(256), 0, as_stream(stream), h, g, rows, ip);
+  return launch_status();
+}
+extern "C" int mca_geglu_fwd_saved(uint16_t* s, uint16_t* g, int64_t rows, int ip, mca_stream_t stream) {
+  if (!s || !g || rows < 0 || ip <= 0 || ip % 8) return MCA_E_BADARG;
+  if (rows == 0) return MCA_OK;
+  hipLaunchKernelGGL(geglu_fwd_kernel<true>, dim3(stream_grid(rows * (ip / 8))), dim3(256), 0, as_stream(stream), s, g, rows, ip);
   return launch_status();
 }
 extern "C" int mca_geglu_bwd(const uint16_t* dg, const uint16_t* h, uint16_t* dh, int64_t rows, int ip,
                              mca_stream_t stream) {
   if (!dg || !h || !dh || rows < 0 || ip <= 0 || ip % 8) return MCA_E_BADARG;
   if (rows == 0) return MCA_OK;
-  hipLaunchKernelGGL(geglu_bwd_kernel, dim3(stream_grid(rows * (ip / 8))), dim3(256), 0, as_stream(stream), dg, h, dh, rows, ip);
+  hipLaunchKernelGGL(geglu_bwd_kernel<false>, dim3(stream_grid(rows * (ip / 8))), dim3(256), 0, as_stream(stream), dg, h, dh, rows, ip);
+  return launch_status();
+}
+extern "C" int mca_geglu_bwd_saved(const uint16_t* dg, const uint16_t* s, uint16_t* dh, int64_t rows, int ip,
+                                   mca_stream_t stream) {
+  if (!dg || !s || !dh || rows < 0 || ip <= 0 || ip % 8) return MCA_E_BADARG;
+  if (rows == 0) return MCA_OK;
+  hipLaunchKernelGGL(geglu_bwd_kernel<true>, dim3(stream_grid(rows * (ip / 8))), dim3(256), 0, as_stream(stream), dg, s, dh, rows, ip);
   return launch_status();
 }
 

@@ -5,6 +5,8 @@
 //                                                     bf16 weight copy)
 //   mca_gemm_nt_lnres / _geglu_fwd / _geglu_bwd       the same GEMM with a fused epilogue (residual LayerNorm
 //                                                     recomputed; FF1 + GEGLU; W2 data gradient + GEGLU')
+//   mca_gemm_nt_geglu_fwd_saved / _bwd_saved          the two GEGLU fusions with the backward's factors [gelu(gate) | a gelu'(gate)]
+//                                                     kept in h's place: the backward epilogue only multiplies
 //   mca_gemm_tn_acc C[N,K] += A[R,N]^T · B[R,K]      both operands reduction-major (weight gradient:
 //                                                     dW = dY^T · X), operands fetched from LDS with the
 //                                                     gfx950 transposed read ds_read_b64_tr_b16
@@ -57,6 +59,9 @@ __device__ __forceinline__ int nt_off(int r, int c) { return r * 64 + ((c ^ ((r 
 
 // Fused GEGLU backward (model.py:35-38 autograd) for 8 consecutive columns n..n+7 of row m of dg = dY·W2 (fp32 in v):
 // h = [a | gate] (bf16, row stride ldh, halves ip apart);  dh_a = dg*gelu(gate),  dh_gate = dg*a*gelu'(gate).
+// SAVED: h holds the saved factors s = [gelu(gate) | a*gelu'(gate)] of the forward (mca_gemm_nt_geglu_fwd_saved) instead:
+// dh_a = dg*s_lo, dh_gate = dg*s_hi.
+template <bool SAVED>
 __device__ __forceinline__ void geglu_bwd_piece(const float (&v)[8], const u16* __restrict__ h, u16* __restrict__ dh, int64_t ldh,
                                                 int ip, int64_t m, int n) {
   const bf16x8 av = *reinterpret_cast<const bf16x8*>(h + m * ldh + n);
@@ -65,6 +70,11 @@ __device__ __forceinline__ void geglu_bwd_piece(const float (&v)[8], const u16* 
 #pragma unroll
   for (int e = 0; e < 8; e++) {
     const float g = bf2f((u16)gv[e]), a = bf2f((u16)av[e]);
+    if (SAVED) {
+      da[e] = (short)f2bf(v[e] * a);
+      dgt[e] = (short)f2bf(v[e] * g);
+      continue;
+    }
     float ge, dge;
     gelu_pair(g, ge, dge);
     da[e] = (short)f2bf(v[e] * ge);
@@ -99,9 +109,9 @@ __device__ __forceinline__ void nt_epilogue_rows(const float* __restrict__ cs, v
       v[e] = t[0]; v[e + 1] = t[1]; v[e + 2] = t[2]; v[e + 3] = t[3];
     }
     const bool full = n + EPT <= N;
-    if (EPI == 1) {          // GEGLU backward: Cv = dh, residual = h (bf16), ldres = row stride of both, N = ip (multiple of 8)
-      if (OUT_BF16) geglu_bwd_piece(reinterpret_cast<const float(&)[8]>(v), reinterpret_cast<const u16*>(residual),
-                                    reinterpret_cast<u16*>(Cv), ldres, N, (int64_t)m, n);
+    if (EPI == 1 || EPI == 3) {          // GEGLU backward: Cv = dh, residual = h (EPI 3: the saved factors s), bf16, ldres = row stride of both, N = ip (multiple of 8)
+      if (OUT_BF16) geglu_bwd_piece<EPI == 3>(reinterpret_cast<const float(&)[8]>(v), reinterpret_cast<const u16*>(residual),
+                                              reinterpret_cast<u16*>(Cv), ldres, N, (int64_t)m, n);
       continue;
     }
     if (bias) {
@@ -500,7 +510,9 @@ MCA_TRACE_BUFFER(gemm)
 // MODE 0: bf16 out;  1: fp32 out;  2: fp32 out + full-row fp32 residual;  3: fused GEGLU backward (bf16 out, see
 // mca_gemm_nt_geglu_bwd: C = dh, residual = h, ldres = row stride of both, N = ip);  4: fused GEGLU forward (see
 // mca_gemm_nt_geglu_fwd: B = W1 [2*ip, K], a column tile = 64 "a" rows + the 64 "gate" rows of the same columns,
-// C = h [M, 2*ip] bf16, residual = g [M, ip] bf16 with row stride ldres, N = ip, tiles_n = ip / 64)
+// C = h [M, 2*ip] bf16, residual = g [M, ip] bf16 with row stride ldres, N = ip, tiles_n = ip / 64);  5 and 6: modes 3 and 4 with
+// the saved factors s = [gelu(gate) | a * gelu'(gate)] in the place of h (mca_gemm_nt_geglu_bwd_saved / _fwd_saved): the same
+// loads and stores per tile, so NST / NLD / NPRE and every counted wait are those of modes 3 and 4
 template <int MODE, bool BIAS>
 __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
     const u16* __restrict__ A, int64_t lda, const u16* __restrict__ B, int64_t ldb, void* __restrict__ Cv,
@@ -508,9 +520,10 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
     int M, int N, int K, int tiles_n, int nwg, int dbg) {
   extern __shared__ __attribute__((aligned(16))) u16 lds2[];
   constexpr int STAGE = (BM2 + BN) * 64;          // elements per stage: A tile then B tile
-  constexpr int NST = MODE == 0 ? 8 : (MODE == 4 ? 12 : 16);         // global stores per wave and tile
-  constexpr int NPRE = (MODE == 2 || MODE == 3) ? 16 : 1;
-  constexpr int NLD = ((MODE == 2 || MODE == 3) ? 16 : 0) + (BIAS ? (MODE == 0 ? 2 : 1) : 0);          // epilogue input loads per wave and tile
+  constexpr bool BWD = MODE == 3 || MODE == 5, FWD = MODE == 4 || MODE == 6, SAVED = MODE >= 5;
+  constexpr int NST = MODE == 0 ? 8 : (FWD ? 12 : 16);         // global stores per wave and tile
+  constexpr int NPRE = (MODE == 2 || BWD) ? 16 : 1;
+  constexpr int NLD = ((MODE == 2 || BWD) ? 16 : 0) + (BIAS ? (MODE == 0 ? 2 : 1) : 0);          // epilogue input loads per wave and tile
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, lh = lane >> 5;
@@ -537,7 +550,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
     for (int i = 0; i < 2; i++) {
       const int p = (i * 8 + wave) * 64 + lane, r = p >> 3, c = (p & 7) ^ gl_sw<64>(r);
       // N % 128 == 0 (MODE 4: N % 64 == 0): no clamp.  MODE 4: tile rows 0..63 = "a" rows, 64..127 = "gate" rows
-      const int rb = MODE == 4 ? (r < 64 ? tn * 64 + r : N + tn * 64 + (r - 64)) : n0 + r;
+      const int rb = FWD ? (r < 64 ? tn * 64 + r : N + tn * 64 + (r - 64)) : n0 + r;
       gb[i] = B + (int64_t)rb * ldb + c * 8;
     }
   };
@@ -575,7 +588,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
         for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
     // ---------------- k-loop: three-stage ring, DMA two k-steps ahead (as gemm_nt_256_kernel) ----------------
     // this wave's 64x64 block (MODE 4: columns of h: "a" part for wn = 0, "gate" part for wn = 1)
-    const int mw = m0 + wm * 64, nw = MODE == 4 ? (wn == 0 ? tn * 64 : N + tn * 64) : n0 + wn * 64;
+    const int mw = m0 + wm * 64, nw = FWD ? (wn == 0 ? tn * 64 : N + tn * 64) : n0 + wn * 64;
     const bool edge = m0 + BM2 > M;
     u32x4v pre[NPRE];                              // residual (fp32) / h (bf16 a | gate) pieces of this lane
     u32x4v bvec[2];
@@ -597,7 +610,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
             PS_GLOAD(pre[(i * 8 + u) % NPRE], residual + (int64_t)m * ldres + nw + 4 * (lane & 15));
           }
       }
-      if (MODE == 3) {
+      if (BWD) {
         const u16* h = reinterpret_cast<const u16*>(residual);
 #pragma unroll
         for (int i = 0; i < 2; i++)
@@ -632,7 +645,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
     // MFMA results and inserts no wait states (it does for its own v_cvt_pk in the bf16 modes).  The last four MFMAs were
     // issued just before the barrier and take 4 x 32 cycles; without a next tile nothing else sits in between (a
     // one-tile-per-workgroup launch returned stale accumulators once in a few runs).
-    if (MODE != 0 && MODE != 4)
+    if (MODE != 0 && !FWD)
       asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
     PS_STAMP();
     // ---------------- epilogue: acc[i][j][4q + e] = C[mw + 32i + l31][nw + 32j + 8q + 4lh + e] ----------------
@@ -646,7 +659,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
     }
     if (NLD > 0) { if (has_next) ps_wait_vm<12>(); else ps_wait_vm<0>(); }          // the epilogue's loads have landed (requested 3 k-steps ago)
     PS_STAMP();
-    if (MODE == 0 || MODE == 4) {
+    if (MODE == 0 || FWD) {
       // bf16 payload: 64 rows x 128 B; 16-byte chunk c of row r at chunk c ^ (r & 7)
 #pragma unroll
       for (int i = 0; i < 2; i++)
@@ -659,15 +672,16 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
             const int row = i * 32 + l31, ch = j * 4 + q;
             PS_DSW64(scratch + (unsigned)(row * 128 + ((ch ^ (row & 7)) << 4) + 8 * lh), pk);
           }
-      u32x4v o[8];
+      // (SAVED: the wave's own block is not stored: the partner phase below writes the factors into h's place)
+      u32x4v o[SAVED ? 1 : 8];
 #pragma unroll
-      for (int u = 0; u < 8; u++) {
+      for (int u = 0; u < (SAVED ? 0 : 8); u++) {
         const int row = (lane >> 3) + 8 * u, ch = lane & 7;
         NT_DSREAD(o[u], scratch + (unsigned)(row * 128 + ((ch ^ (row & 7)) << 4)));
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (!SAVED) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-      for (int u = 0; u < 8; u++) {
+      for (int u = 0; u < (SAVED ? 0 : 8); u++) {
         const int m = mw + (lane >> 3) + 8 * u;
         if (BIAS) {          // the accumulators were rounded before the bias: add it and round again (bias GEMMs write fp32 in this model)
           float f[8];
@@ -681,9 +695,11 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
         u16* cp = reinterpret_cast<u16*>(Cv) + (int64_t)m * ldc + nw + 8 * (lane & 7);
         if (m < M) PS_GSTORE(cp, o[u]);
       }
-      if (MODE == 4) {
+      if (FWD) {
         // g = a * gelu(gate): the partner wave (same rows, other column half) holds the other operand: both blocks are
         // in the scratch areas now; wave wn takes rows 32*wn .. 32*wn + 31 of the pair's 64 rows
+        // SAVED: and the two factors of the backward, s = [gelu(gate) | a * gelu'(gate)], into the columns of C that a and gate
+        // would have taken: three stores per u, 12 per tile like the eight own-block stores + four g stores of the unsaved form
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         const unsigned sa = lds_base + 2u * (unsigned)(STAGE * 2) + (unsigned)(wave & ~1) * 8192u, sg = sa + 8192u;
         u32x4v av[4], gv[4];
@@ -698,16 +714,21 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
 #pragma unroll
         for (int u = 0; u < 4; u++) {
           const int m = m0 + wm * 64 + 32 * wn + (lane >> 3) + 8 * u;
-          u32x4v gg;
+          u32x4v gg, slo, shi;
 #pragma unroll
           for (int e = 0; e < 4; e++) {
             const float a0 = __uint_as_float(av[u][e] << 16), a1 = __uint_as_float(av[u][e] & 0xffff0000u);
             const float g0 = __uint_as_float(gv[u][e] << 16), g1 = __uint_as_float(gv[u][e] & 0xffff0000u);
-            float ge0, ge1, unused;
-            gelu_pair(g0, ge0, unused); gelu_pair(g1, ge1, unused);
+            float ge0, ge1, dge0, dge1;
+            gelu_pair(g0, ge0, dge0); gelu_pair(g1, ge1, dge1);
             gg[e] = pack2bf(a0 * ge0, a1 * ge1);
+            if (SAVED) { slo[e] = pack2bf(ge0, ge1); shi[e] = pack2bf(a0 * dge0, a1 * dge1); }
           }
           u16* gp = gout + (int64_t)m * ldres + tn * 64 + 8 * (lane & 7);
+          if (SAVED) {
+            u16* sp = reinterpret_cast<u16*>(Cv) + (int64_t)m * ldc + tn * 64 + 8 * (lane & 7);
+            if (m < M) { PS_GSTORE(sp, slo); PS_GSTORE(sp + N, shi); }
+          }
           if (m < M) PS_GSTORE(gp, gg);
         }
       }
@@ -725,7 +746,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
             const int ch = j * 8 + 2 * q + lh;
             PS_DSW128(scratch + (unsigned)(l31 * 256 + ((ch ^ (l31 & 15)) << 4)), w);
           }
-        if (MODE != 3) {
+        if (!BWD) {
           u32x4v o[8];
 #pragma unroll
           for (int u = 0; u < 8; u++) {
@@ -767,6 +788,11 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
               const float d0 = __uint_as_float(o[u][e >> 1][2 * (e & 1)]), d1 = __uint_as_float(o[u][e >> 1][2 * (e & 1) + 1]);
               const float a0 = __uint_as_float(av[e] << 16), a1 = __uint_as_float(av[e] & 0xffff0000u);
               const float g0 = __uint_as_float(gv[e] << 16), g1 = __uint_as_float(gv[e] & 0xffff0000u);
+              if (SAVED) {          // av = s_lo = gelu(gate), gv = s_hi = a * gelu'(gate): the forward's saved factors
+                da[e] = pack2bf(d0 * a0, d1 * a1);
+                dgt[e] = pack2bf(d0 * g0, d1 * g1);
+                continue;
+              }
               float ge0, dge0, ge1, dge1;
               gelu_pair(g0, ge0, dge0); gelu_pair(g1, ge1, dge1);
               da[e] = pack2bf(d0 * ge0, d1 * ge1);
@@ -796,7 +822,9 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
 // ---------------------------------------------------------------------------------------------------------
 // GEGLU = true: fused FF1 + GEGLU forward (see mca_gemm_nt_geglu_fwd): B = W1 [2*N, K] with N = ip, a column tile = 128 "a"
 // rows + the 128 "gate" rows of the same columns (wave column wn = 0 holds a, wn = 1 gate), C = h [M, 2*N], G = g [M, N].
-template <bool GEGLU>
+// SAVED (with GEGLU): C = s = [gelu(gate) | a * gelu'(gate)], the backward's factors, in h's place (mca_gemm_nt_geglu_fwd_saved):
+// the 16 own-block stores of a tile are not made and the partner phase stores s_lo, s_hi and g: 24 stores as before.
+template <bool GEGLU, bool SAVED = false>
 __global__ __launch_bounds__(512) void gemm_nt_persist256_kernel(
     const u16* __restrict__ A, int64_t lda, const u16* __restrict__ B, int64_t ldb, u16* __restrict__ C, int64_t ldc,
     u16* __restrict__ G, int64_t ldg, int M, int N, int K, int tiles_n, int nwg, int dbg) {
@@ -934,15 +962,15 @@ __global__ __launch_bounds__(512) void gemm_nt_persist256_kernel(
           const int ch = j * 4 + q;
           PS_DSW64(scratch + (unsigned)(l31 * 256 + ((ch ^ (l31 & 15)) << 4) + 8 * lh), pk);
         }
-      u32x4v o[8];
+      u32x4v o[SAVED ? 1 : 8];
 #pragma unroll
-      for (int u = 0; u < 8; u++) {
+      for (int u = 0; u < (SAVED ? 0 : 8); u++) {
         const int row = (lane >> 4) + 4 * u, ch = lane & 15;
         NT_DSREAD(o[u], scratch + (unsigned)(row * 256 + ((ch ^ (row & 15)) << 4)));
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (!SAVED) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-      for (int u = 0; u < 8; u++) {
+      for (int u = 0; u < (SAVED ? 0 : 8); u++) {
         const int m = mw + i * 32 + (lane >> 4) + 4 * u;
         u16* cp = C + (int64_t)m * ldc + nw + 8 * (lane & 15);
         if (m < M) PS_GSTORE(cp, o[u]);
@@ -963,16 +991,21 @@ __global__ __launch_bounds__(512) void gemm_nt_persist256_kernel(
 #pragma unroll
         for (int u = 0; u < 4; u++) {
           const int m = m0 + wm * 64 + i * 32 + 16 * wn + (lane >> 4) + 4 * u;
-          u32x4v gg;
+          u32x4v gg, slo, shi;
 #pragma unroll
           for (int e = 0; e < 4; e++) {
             const float a0 = __uint_as_float(av[u][e] << 16), a1 = __uint_as_float(av[u][e] & 0xffff0000u);
             const float g0 = __uint_as_float(gv[u][e] << 16), g1 = __uint_as_float(gv[u][e] & 0xffff0000u);
-            float ge0, ge1, unused;
-            gelu_pair(g0, ge0, unused); gelu_pair(g1, ge1, unused);
+            float ge0, ge1, dge0, dge1;
+            gelu_pair(g0, ge0, dge0); gelu_pair(g1, ge1, dge1);
             gg[e] = pack2bf(a0 * ge0, a1 * ge1);
+            if (SAVED) { slo[e] = pack2bf(ge0, ge1); shi[e] = pack2bf(a0 * dge0, a1 * dge1); }
           }
           u16* gp = G + (int64_t)m * ldg + tn * 128 + 8 * (lane & 15);
+          if (SAVED) {
+            u16* sp = C + (int64_t)m * ldc + tn * 128 + 8 * (lane & 15);
+            if (m < M) { PS_GSTORE(sp, slo); PS_GSTORE(sp + N, shi); }
+          }
           if (m < M) PS_GSTORE(gp, gg);
         }
         if (i == 0) asm volatile("s_barrier" ::: "memory");          // the partner has read this row block: scratch may be overwritten
@@ -1567,10 +1600,10 @@ static int launch_persist(const mca_gemm_plan& p, const gemm_operands& o, mca_st
   return launch_kernel<gemm_nt_persist_kernel<MODE, BIAS>>(p, s, o.A, o.lda, o.B, o.ldb, o.C, o.ldc, o.bias, o.residual, o.ldres, o.M, p.n, o.K,
                                                            p.tiles_n, p.nwg, p.dbg);
 }
-template <bool GEGLU>
+template <bool GEGLU, bool SAVED = false>
 static int launch_persist256(const mca_gemm_plan& p, const gemm_operands& o, mca_stream_t s) {
   u16* g = GEGLU ? reinterpret_cast<u16*>(const_cast<float*>(o.residual)) : nullptr;
-  return launch_kernel<gemm_nt_persist256_kernel<GEGLU>>(p, s, o.A, o.lda, o.B, o.ldb, reinterpret_cast<u16*>(o.C), o.ldc, g,
+  return launch_kernel<gemm_nt_persist256_kernel<GEGLU, SAVED>>(p, s, o.A, o.lda, o.B, o.ldb, reinterpret_cast<u16*>(o.C), o.ldc, g,
                                                          GEGLU ? o.ldres : (int64_t)0, o.M, p.n, o.K, p.tiles_n, p.nwg, p.dbg);
 }
 template <auto KERNEL>
@@ -1606,6 +1639,11 @@ static int launch(const mca_gemm_plan& p, const gemm_operands& o, mca_stream_t s
     case MCA_GK_NT_PERSIST_GEGLU_FWD: return launch_persist<4, false>(p, o, s);
     case MCA_GK_NT_PERSIST256: return launch_persist256<false>(p, o, s);
     case MCA_GK_NT_PERSIST256_GEGLU_FWD: return launch_persist256<true>(p, o, s);
+    case MCA_GK_NT_GLDS_GEGLU_BWD_SAVED: return launch_glds<true, 0, 3>(p, o, s);
+    case MCA_GK_NT_256_GEGLU_BWD_SAVED: return launch_256<true, 0, 0, 3>(p, o, s);
+    case MCA_GK_NT_PERSIST_GEGLU_BWD_SAVED: return launch_persist<5, false>(p, o, s);
+    case MCA_GK_NT_PERSIST_GEGLU_FWD_SAVED: return launch_persist<6, false>(p, o, s);
+    case MCA_GK_NT_PERSIST256_GEGLU_FWD_SAVED: return launch_persist256<true, true>(p, o, s);
     case MCA_GK_TN: return launch_tn<gemm_tn_kernel<false>>(p, o, s);
     case MCA_GK_TN_256: return launch_tn<gemm_tn_256_kernel<false>>(p, o, s);
     case MCA_GK_TN_256X256: return launch_tn<gemm_tn_256x256_kernel<false>>(p, o, s);
@@ -1654,28 +1692,39 @@ extern "C" int mca_gemm_nt_lnres(const uint16_t* A, int64_t lda, const uint16_t*
 
 // dh = GEGLU'(h) applied to dg = A·B^T without materialising dg (fused epilogue).  A[M,K] (= d x_out, bf16), B[ip,K] (= W2^T
 // copy), h / dh [M, 2*ip] bf16.
-extern "C" int mca_gemm_nt_geglu_bwd(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const uint16_t* h,
-                                     uint16_t* dh, int64_t ldh, int64_t ip, int64_t M, int64_t K, mca_stream_t stream) {
+// (saved: h holds the forward's saved factors s, include/mca_hip.h)
+static int geglu_bwd_entry(bool saved, const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const uint16_t* h,
+                           uint16_t* dh, int64_t ldh, int64_t ip, int64_t M, int64_t K, mca_stream_t stream) {
   if (!A || !B || !h || !dh || M <= 0 || ip <= 0 || K <= 0) return MCA_E_BADARG;
   if (K % 64 || lda % 8 || ldb % 8 || ldh % 8 || ip % 8 || (uintptr_t)A % 16 || (uintptr_t)B % 16 || (uintptr_t)h % 16 || (uintptr_t)dh % 16)
     return MCA_E_ALIGN;
   if (lda < K || ldb < K || ldh < 2 * ip) return MCA_E_BADARG;
   if (M > (1LL << 30)) return MCA_E_UNSUPPORTED;
   const gemm_operands o = {A, lda, B, ldb, dh, ldh, nullptr, reinterpret_cast<const float*>(h), ldh, 0, nullptr, nullptr, nullptr, (int)M, (int)K, nullptr};
-  return launch(mca_plan_gemm_nt_geglu_bwd(M, ip, K, mca_knobs, num_cus()), o, stream);
+  return launch(saved ? mca_plan_gemm_nt_geglu_bwd_saved(M, ip, K, mca_knobs, num_cus()) : mca_plan_gemm_nt_geglu_bwd(M, ip, K, mca_knobs, num_cus()),
+                o, stream);
+}
+extern "C" int mca_gemm_nt_geglu_bwd(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const uint16_t* h,
+                                     uint16_t* dh, int64_t ldh, int64_t ip, int64_t M, int64_t K, mca_stream_t stream) {
+  return geglu_bwd_entry(false, A, lda, B, ldb, h, dh, ldh, ip, M, K, stream);
+}
+extern "C" int mca_gemm_nt_geglu_bwd_saved(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const uint16_t* s,
+                                           uint16_t* dh, int64_t ldh, int64_t ip, int64_t M, int64_t K, mca_stream_t stream) {
+  return geglu_bwd_entry(true, A, lda, B, ldb, s, dh, ldh, ip, M, K, stream);
 }
 
 // h = A·W1^T (bf16, [a | gate]) and g = a * gelu(gate) in one pass (persistent kernels); small or oddly shaped
 // problems take the plain GEMM followed by the element-wise kernel.
-extern "C" int mca_gemm_nt_geglu_fwd(const uint16_t* A, int64_t lda, const uint16_t* W1, int64_t ldb, uint16_t* h, int64_t ldh,
-                                     uint16_t* g, int64_t ldg, int64_t ip, int64_t M, int64_t K, mca_stream_t stream) {
+// (saved: h receives the saved factors s instead, include/mca_hip.h)
+static int geglu_fwd_entry(bool saved, const uint16_t* A, int64_t lda, const uint16_t* W1, int64_t ldb, uint16_t* h, int64_t ldh,
+                           uint16_t* g, int64_t ldg, int64_t ip, int64_t M, int64_t K, mca_stream_t stream) {
   if (!A || !W1 || !h || !g || M <= 0 || ip <= 0 || K <= 0) return MCA_E_BADARG;
   if (K % 64 || lda % 8 || ldb % 8 || ldh % 8 || ldg % 8 || ip % 8 || (uintptr_t)A % 16 || (uintptr_t)W1 % 16 || (uintptr_t)h % 16 ||
       (uintptr_t)g % 16)
     return MCA_E_ALIGN;
   if (lda < K || ldb < K || ldh < 2 * ip || ldg < ip) return MCA_E_BADARG;
   if (M > (1LL << 30)) return MCA_E_UNSUPPORTED;
-  const mca_gemm_plan p = mca_plan_gemm_nt_geglu_fwd(M, ip, K, mca_knobs, num_cus());
+  const mca_gemm_plan p = saved ? mca_plan_gemm_nt_geglu_fwd_saved(M, ip, K, mca_knobs, num_cus()) : mca_plan_gemm_nt_geglu_fwd(M, ip, K, mca_knobs, num_cus());
   if (p.kernel != MCA_GK_NONE) {
     const gemm_operands o = {A, lda, W1, ldb, h, ldh, nullptr, reinterpret_cast<const float*>(g), ldg, 0, nullptr, nullptr, nullptr, (int)M, (int)K, nullptr};
     return launch(p, o, stream);
@@ -1683,7 +1732,15 @@ extern "C" int mca_gemm_nt_geglu_fwd(const uint16_t* A, int64_t lda, const uint1
   if (ldg != ip || ldh != 2 * ip) return MCA_E_UNSUPPORTED;          // the element-wise kernel takes packed rows
   const int rc = mca_gemm_nt(A, lda, W1, ldb, h, ldh, 1, nullptr, nullptr, 0, 0, M, 2 * ip, K, stream);
   if (rc != MCA_OK) return rc;
-  return mca_geglu_fwd(h, g, M, (int)ip, stream);
+  return saved ? mca_geglu_fwd_saved(h, g, M, (int)ip, stream) : mca_geglu_fwd(h, g, M, (int)ip, stream);
+}
+extern "C" int mca_gemm_nt_geglu_fwd(const uint16_t* A, int64_t lda, const uint16_t* W1, int64_t ldb, uint16_t* h, int64_t ldh,
+                                     uint16_t* g, int64_t ldg, int64_t ip, int64_t M, int64_t K, mca_stream_t stream) {
+  return geglu_fwd_entry(false, A, lda, W1, ldb, h, ldh, g, ldg, ip, M, K, stream);
+}
+extern "C" int mca_gemm_nt_geglu_fwd_saved(const uint16_t* A, int64_t lda, const uint16_t* W1, int64_t ldb, uint16_t* s, int64_t lds,
+                                           uint16_t* g, int64_t ldg, int64_t ip, int64_t M, int64_t K, mca_stream_t stream) {
+  return geglu_fwd_entry(true, A, lda, W1, ldb, s, lds, g, ldg, ip, M, K, stream);
 }
 
 static int check_tn(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* C, int64_t ldc, int64_t N, int64_t K) {
@@ -1824,6 +1881,8 @@ extern "C" int mca_dbg_plan_gemm_nt(int entry, const mca_nt_problem* pr, int cus
       *out = mca_plan_gemm_nt_lnres(pr->M, pr->N); return MCA_OK;
     case 2: *out = mca_plan_gemm_nt_geglu_fwd(pr->M, pr->N, pr->K, mca_knobs, cus); return MCA_OK;
     case 3: *out = mca_plan_gemm_nt_geglu_bwd(pr->M, pr->N, pr->K, mca_knobs, cus); return MCA_OK;
+    case 4: *out = mca_plan_gemm_nt_geglu_fwd_saved(pr->M, pr->N, pr->K, mca_knobs, cus); return MCA_OK;
+    case 5: *out = mca_plan_gemm_nt_geglu_bwd_saved(pr->M, pr->N, pr->K, mca_knobs, cus); return MCA_OK;
   }
   return MCA_E_BADARG;
 }

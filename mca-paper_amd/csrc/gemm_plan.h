@@ -41,7 +41,15 @@ enum mca_gemm_kernel {
   MCA_GK_TN_256 = 28,                  // gemm_tn_256_kernel
   MCA_GK_TN_256X256 = 29,              // gemm_tn_256x256_kernel
   MCA_GK_TN_256X256_GROUP = 30,        // gemm_tn_256x256_group_kernel
-  MCA_GK_COUNT = 31
+  MCA_GK_COUNT = 31,
+  // The saved-factor GEGLU forms (mca_gemm_nt_geglu_fwd_saved / _bwd_saved): the value of the unsaved sibling + MCA_GK_SAVED.
+  // They stand outside the table above (MCA_GK_COUNT counts the base forms), so no existing value, name or count moves.
+  MCA_GK_SAVED = 64,
+  MCA_GK_NT_GLDS_GEGLU_BWD_SAVED = MCA_GK_SAVED + MCA_GK_NT_GLDS_GEGLU_BWD,              // gemm_nt_glds_kernel<true, 0, 64, 3>
+  MCA_GK_NT_256_GEGLU_BWD_SAVED = MCA_GK_SAVED + MCA_GK_NT_256_GEGLU_BWD,                // gemm_nt_256_kernel<true, 0, 0, 3>
+  MCA_GK_NT_PERSIST_GEGLU_BWD_SAVED = MCA_GK_SAVED + MCA_GK_NT_PERSIST_GEGLU_BWD,        // gemm_nt_persist_kernel<5, false>
+  MCA_GK_NT_PERSIST_GEGLU_FWD_SAVED = MCA_GK_SAVED + MCA_GK_NT_PERSIST_GEGLU_FWD,        // gemm_nt_persist_kernel<6, false>
+  MCA_GK_NT_PERSIST256_GEGLU_FWD_SAVED = MCA_GK_SAVED + MCA_GK_NT_PERSIST256_GEGLU_FWD   // gemm_nt_persist256_kernel<true, true>
 };
 
 // the instantiation a value stands for, spelled as in gemm.hip without blanks
@@ -59,6 +67,13 @@ static inline const char* mca_gemm_kernel_name(int k) {
       "gemm_nt_persist_kernel<3,false>", "gemm_nt_persist_kernel<4,false>",
       "gemm_nt_persist256_kernel<false>", "gemm_nt_persist256_kernel<true>",
       "gemm_tn_kernel", "gemm_tn_256_kernel", "gemm_tn_256x256_kernel", "gemm_tn_256x256_group_kernel"};
+  switch (k) {
+    case MCA_GK_NT_GLDS_GEGLU_BWD_SAVED: return "gemm_nt_glds_kernel<true,0,64,3>";
+    case MCA_GK_NT_256_GEGLU_BWD_SAVED: return "gemm_nt_256_kernel<true,0,0,3>";
+    case MCA_GK_NT_PERSIST_GEGLU_BWD_SAVED: return "gemm_nt_persist_kernel<5,false>";
+    case MCA_GK_NT_PERSIST_GEGLU_FWD_SAVED: return "gemm_nt_persist_kernel<6,false>";
+    case MCA_GK_NT_PERSIST256_GEGLU_FWD_SAVED: return "gemm_nt_persist256_kernel<true,true>";
+  }
   return k >= 0 && k < MCA_GK_COUNT ? names[k] : "?";
 }
 
@@ -188,6 +203,20 @@ static inline mca_gemm_plan mca_plan_gemm_nt_geglu_fwd(int64_t M, int64_t ip, in
   pl.n = (int)ip; pl.nwg = (int)((M + BM2 - 1) / BM2) * pl.tiles_n;
   pl.grid_x = mca_min_int(pl.nwg, cus); pl.grid_y = 1; pl.block = 512; pl.dbg = knobs[0];
   return pl;
+}
+
+// The saved-factor forms (mca_gemm_nt_geglu_fwd_saved / _bwd_saved, include/mca_hip.h): the sibling's plan - same grid, block,
+// LDS bytes and integer arguments for every shape, knob table and CU count - with the kernel value swapped for the saved one.
+// MCA_GK_NONE stays MCA_GK_NONE: the plain GEMM followed by mca_geglu_fwd_saved.
+static inline mca_gemm_plan mca_plan_saved(mca_gemm_plan pl) {
+  if (pl.kernel != MCA_GK_NONE) pl.kernel += MCA_GK_SAVED;
+  return pl;
+}
+static inline mca_gemm_plan mca_plan_gemm_nt_geglu_fwd_saved(int64_t M, int64_t ip, int64_t K, const int* knobs, int cus) {
+  return mca_plan_saved(mca_plan_gemm_nt_geglu_fwd(M, ip, K, knobs, cus));
+}
+static inline mca_gemm_plan mca_plan_gemm_nt_geglu_bwd_saved(int64_t M, int64_t N, int64_t K, const int* knobs, int cus) {
+  return mca_plan_saved(mca_plan_gemm_nt_geglu_bwd(M, N, K, knobs, cus));
 }
 
 // ======================================================================================================================

@@ -47,9 +47,11 @@ def debug_options() -> dict:
     dkv_keys=256 (8-wavefront key blocks in the dK/dV pass), lazy_softmax=0 (the textbook running-maximum recurrence in the forward
     attention instead of MCA_ATTN_LAZY_REFERENCE, the default since round 5: -9 % on that kernel, statistically indistinguishable
     from the textbook form over 8 data seeds, profiles/r05_lazy_softmax_seed_study.txt), deterministic=1 (the fixed-order forms of
-    the weight-gradient, LayerNorm-backward, row-reduction and table-gradient launches: FusionEngine.set_deterministic).  Kernel-level knobs: include/mca_hip_debug.h (hip.knobs)."""
+    the weight-gradient, LayerNorm-backward, row-reduction and table-gradient launches: FusionEngine.set_deterministic),
+    geglu_saved=0 (the FF1 GEMM keeps h = [a | gate] and the backward evaluates gelu again, instead of the saved factors:
+    FusionEngine.geglu_saved_factors).  Kernel-level knobs: include/mca_hip_debug.h (hip.knobs)."""
     opts = {"overlap_wgrad": None, "group_wgrad": True, "mask_mfma": True, "dkv_keys": 128, "lazy_softmax": True,
-            "onepass": None, "deterministic": False}          # onepass=0|1: the one-pass attention backward (attention_bwd1.hip); default: by size
+            "onepass": None, "deterministic": False, "geglu_saved": True}          # onepass=0|1: the one-pass attention backward (attention_bwd1.hip); default: by size
     for item in filter(None, os.environ.get("MCA_DEBUG", "").split(",")):
         k, _, v = item.partition("=")
         k = k.strip()
@@ -114,6 +116,11 @@ class FusionEngine:
         self._flag_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         self._flag_event: Optional[torch.cuda.Event] = None
         self.fuse_geglu_bwd = True
+        # The FF1 epilogue stores the two factors of the GEGLU backward, s = [gelu(gate) | a * gelu'(gate)], where h = [a | gate]
+        # would go (mca_gemm_nt_geglu_fwd_saved), and the fused backward only multiplies by them.  Read once per forward
+        # (forward_trunk), and only with fuse_geglu_bwd: the unfused backward reads the true h.  What a layer's buffer holds is
+        # recorded on its workspace (a["h_holds"]) and asserted by the backward.
+        self.geglu_saved_factors = bool(self.dbg["geglu_saved"])
         self._mod_shifts = torch.arange(len(model.modality_types), dtype=torch.int32, device=self.device)
         self.fuse_ln_residual = True                # residual LayerNorm recomputed in the GEMM epilogue (large batches)
         # Weight-gradient GEMMs on a side stream, concurrent with the backward chain: None = by size (on below OVERLAP_ROWS_MAX
@@ -393,7 +400,8 @@ class FusionEngine:
                              o=bf(T, D), lse=f32(b, H, N), x1n_b=bf(T, D), h=bf(T, 2 * Ip), g=bf(T, Ip),
                              # backward operands of the weight-gradient GEMMs: one set PER LAYER, so those GEMMs can run
                              # on a side stream without write-after-read hazards against the next layer's backward
-                             dxo_b=bf(T, D), dx1_b=bf(T, D), dh=bf(T, 2 * Ip), dqkv=bf(T, 3 * D))
+                             dxo_b=bf(T, D), dx1_b=bf(T, D), dh=bf(T, 2 * Ip), dqkv=bf(T, 3 * D),
+                             h_holds=None)          # "h" = [a | gate] or "s" = the saved GEGLU factors: set by forward_trunk
                         for _ in range(self.L)]
         ws["xn"], ws["x1n"] = f32(T, D), f32(T, D)
         ws["mf"], ws["rf"] = f32(T), f32(T)
@@ -649,6 +657,8 @@ class FusionEngine:
         # T >= 2048: the residual LayerNorm(x) is recomputed inside the out-proj / FF2 GEMM epilogues from x and the saved row
         # statistics (mca_gemm_nt_lnres): the LayerNorm kernels then write the bf16 GEMM operand only
         ln_in_gemm = self.fuse_ln_residual and T >= 2048 and D % 128 == 0 and D >= 512 and Ip >= 512
+        saved = self.geglu_saved_factors and self.fuse_geglu_bwd
+        ff1 = "mca_gemm_nt_geglu_fwd_saved" if saved else "mca_gemm_nt_geglu_fwd"
         for i, ly in enumerate(m.layers):
             w, a = self.wl[i], ws["layers"][i]
             xin, xout = ws["x"][i], ws["x"][i + 1]
@@ -662,9 +672,11 @@ class FusionEngine:
             else:
                 self.gemm_nt(a["o"], w["o"], a["x1"], T, D, D, residual=ws["xn"])
             self.ln_fwd(a["x1"], g, T, D, a["m2"], a["r2"], y=None if ln_in_gemm else ws["x1n"], ldy=D, y_bf16=a["x1n_b"], cols_pad=D)
-            # h = x1n @ W1^T and g = GEGLU(h) in one pass (h is kept for the backward, not read back here)
-            call("mca_gemm_nt_geglu_fwd", ptr(a["x1n_b"]), D, ptr(w["w1"]), D, ptr(a["h"]), 2 * Ip, ptr(a["g"]), Ip, Ip, T, D,
-                 stream_ptr(), flops=2.0 * T * 2 * Ip * D)
+            # h = x1n @ W1^T and g = GEGLU(h) in one pass (h, or the backward's factors s in its place, is kept for the
+            # backward, not read back here)
+            a["h_holds"] = "s" if saved else "h"
+            call(ff1, ptr(a["x1n_b"]), D, ptr(w["w1"]), D, ptr(a["h"]), 2 * Ip, ptr(a["g"]), Ip, Ip, T, D,
+                 stream_ptr(), flops=2.0 * T * 2 * Ip * D, profile_as="mca_gemm_nt_geglu_fwd")
             if ln_in_gemm:
                 call("mca_gemm_nt_lnres", ptr(a["g"]), Ip, ptr(w["w2"]), Ip, ptr(xout), D, ptr(a["x1"]), D, ptr(a["m2"]), ptr(a["r2"]),
                      ptr(g.data), T, D, Ip, stream_ptr(), flops=2.0 * T * D * Ip)
@@ -826,10 +838,15 @@ class FusionEngine:
             grouped = self.group_wgrad and T >= 4096
             if not grouped:
                 on_side(lambda dxo=dxo, a=a, ly=ly: tn(dxo, a["g"], G(ly.ff.feedforward[2].weight), T, D, I))
+            # the layer's buffer holds what this backward is about to read it as: a flag switched between forward and backward
+            # would otherwise hand the saved factors to a kernel that takes them for h, or the other way round
+            saved = self.geglu_saved_factors and self.fuse_geglu_bwd
+            assert a["h_holds"] == ("s" if saved else "h"), \
+                f"layer {i}: the forward left {a['h_holds']!r} in the GEGLU buffer; geglu_saved_factors / fuse_geglu_bwd changed since"
             if self.fuse_geglu_bwd:
                 # dh = GEGLU'(h) * (dx @ W2): the (T, Ip) intermediate dg is never written (fused GEMM epilogue)
-                call("mca_gemm_nt_geglu_bwd", ptr(dxo), D, ptr(w["w2T"]), D, ptr(a["h"]), ptr(dh), 2 * Ip, Ip, T, D,
-                     stream_ptr(), flops=2.0 * T * Ip * D)
+                call("mca_gemm_nt_geglu_bwd_saved" if saved else "mca_gemm_nt_geglu_bwd", ptr(dxo), D, ptr(w["w2T"]), D,
+                     ptr(a["h"]), ptr(dh), 2 * Ip, Ip, T, D, stream_ptr(), flops=2.0 * T * Ip * D, profile_as="mca_gemm_nt_geglu_bwd")
             else:
                 self.gemm_nt(dxo, w["w2T"], ws["dg"], T, Ip, D)
                 call("mca_geglu_bwd", ptr(ws["dg"]), ptr(a["h"]), ptr(dh), T, Ip, stream_ptr())

@@ -156,7 +156,8 @@ class TnGroupDetPlan(C.Structure):
     _fields_ = [("plan", TnGroupPlan), ("slots", C.c_int), ("slot_stride", C.c_int64), ("scratch_floats", C.c_int64)]
 
 
-PLAN_NT, PLAN_LNRES, PLAN_GEGLU_FWD, PLAN_GEGLU_BWD = range(4)          # `entry` of mca_dbg_plan_gemm_nt
+PLAN_NT, PLAN_LNRES, PLAN_GEGLU_FWD, PLAN_GEGLU_BWD, PLAN_GEGLU_FWD_SAVED, PLAN_GEGLU_BWD_SAVED = range(6)          # `entry` of mca_dbg_plan_gemm_nt
+GK_SAVED = 64          # csrc/gemm_plan.h MCA_GK_SAVED: a saved-factor kernel's value is its unsaved sibling's + this
 
 
 # the LayerNorm planners' structs (csrc/ln_plan.h; filled by mca_dbg_plan_layernorm_fwd / _bwd).  Pointers travel as integers.
@@ -197,6 +198,11 @@ SIGNATURES = {
     "mca_gemm_nt_geglu_bwd": (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P]),
     "mca_gemm_nt_lnres": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _P]),
     "mca_gemm_nt_geglu_fwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+    # saved-factor forms: the siblings' argument lists, s in the place of h
+    "mca_gemm_nt_geglu_fwd_saved": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+    "mca_gemm_nt_geglu_bwd_saved": (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P]),
+    "mca_geglu_fwd_saved": (_I, [_P, _P, _I64, _I, _P]),
+    "mca_geglu_bwd_saved": (_I, [_P, _P, _P, _I64, _I, _P]),
     "mca_gemm_tn_acc": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
     "mca_gemm_tn_acc_group": (_I, [_P, _I, _I64, _P]),
     "mca_layernorm_fwd": (_I, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I, _P, _P, _I64, _I, _F, _P]),
@@ -408,13 +414,16 @@ def profile_stop():
     return prof["totals"]
 
 
-def call(name: str, *args, flops: float = 0.0):
+def call(name: str, *args, flops: float = 0.0, profile_as: Optional[str] = None):
+    """profile_as: the key this launch is timed and recorded under instead of its own name: another form of the same
+    operation (the saved-factor GEGLU GEMMs) then stays in the row of the form it replaces, comparable across commits."""
+    key = profile_as or name
     # (a deterministic form is timed wherever its plain form is asked for, under its own name)
-    if PROFILE is not None and _PROFILE_ON and (name in PROFILE["names"] or (name.endswith("_det") and name[:-4] in PROFILE["names"])):
+    if PROFILE is not None and _PROFILE_ON and (key in PROFILE["names"] or (key.endswith("_det") and key[:-4] in PROFILE["names"])):
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
         check(getattr(lib(), name)(*args), name)
         e.record()
-        PROFILE["records"].setdefault(name + ("/" + _TAG if _TAG else ""), []).append((s, e, flops))
+        PROFILE["records"].setdefault(key + ("/" + _TAG if _TAG else ""), []).append((s, e, flops))
         return
     check(getattr(lib(), name)(*args), name)
