@@ -11,26 +11,20 @@
 //   mca_attn_bwd_dkv  one workgroup = a 256-key block (8 wavefronts x 32 keys), sweeping 64-query steps: the one-pass kernel
 //                     without its dS^T image, K image, dQ product and atomics.
 // The price is S and dP computed twice (7 MFMA products instead of 5); both passes are bitwise reproducible.
-#include "common.h"
+#include "attention_common.h"
 
-#define DH 64
-#define AQ 128      // dq pass: query rows per workgroup
-#define AK 64       // dq pass: keys per tile
-#define MAX_KTILES 512
 // dkv pass: W wavefronts per workgroup, 32 keys each: W = 8 (256 keys, one workgroup per CU) or W = 4 (128 keys, two
 // independent workgroups per CU, free to drift apart: 3 % faster at N = 2538, equal at N = 6088); chosen by the caller through
 // mca_attn_bwd2_args.kblock_keys
 #define BQ 64       // dkv pass: query rows per step
 #define MAX_QTILES 2048
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 // [rows][64 d] bf16 image (128-byte rows) serving BOTH ds_read_b128 row reads and ds_read_b64_tr_b16 transposed reads
 __device__ __forceinline__ int rt_off(int r, int c) {
   const int s = ((r >> 1) & 7) ^ (((r >> 1) & 1) << 2);
   return r * 64 + ((c ^ s) << 3);
 }
-// row reads only: chunk c (16 B) of row r at c ^ ((r>>1)&7)
-__device__ __forceinline__ int row_off(int r, int c) { return r * 64 + ((c ^ ((r >> 1) & 7)) << 3); }
+// (row reads only: k_off, attention_common.h)
 
 // =====================================================================================================
 // dQ pass
@@ -47,16 +41,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(mca_attn_bwd2_args 
   u16* Ks = lds;
   u16* Vs = lds + 2 * AK * DH;
 
-  const int lin0 = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-  const int lin = (dbg & 16) ? lin0 : xcd_remap(lin0, (int)(gridDim.x * gridDim.y * gridDim.z));
-  const int qt = a.q_order[lin % (int)gridDim.x];
-  const int h = (lin / (int)gridDim.x) % (int)gridDim.y, b = lin / (int)(gridDim.x * gridDim.y);
+  const auto [lin0, qt, h, b] = attn_wg_decode(a.q_order, dbg);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, lh = lane >> 5;
-  const int q0 = qt * AQ + wave * 32;
-  int qrow = q0 + l31;
-  const bool qvalid = qrow < a.nq;
-  if (qrow > a.nq - 1) qrow = a.nq - 1;
+  bool qvalid;
+  const int qrow = attn_qrow(qt, wave * 32 + l31, a.nq, qvalid);
 
   // B operands held for the whole kernel: lane = query, 8 consecutive d per k-step
   bf16x8 qf[4], dof[4];
@@ -67,10 +56,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(mca_attn_bwd2_args 
     for (int s = 0; s < 4; s++) { qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s); dof[s] = *reinterpret_cast<const bf16x8*>(op + 16 * s); }
   }
   const uint32_t qm = a.qmask[qrow];
-  // the mask as a matrix product (mca_hip.h, mca_build_keyhot): this lane's query-side operand, groups 8 lh .. 8 lh + 7
-  // (rebuilt from qm in every masked tile: four registers held for the whole kernel cost nine spills)
+  // the mask as a matrix product (attention_common.h): this lane's query-side operand is rebuilt from qm8 in every masked
+  // tile: four registers held for the whole kernel cost nine spills
   constexpr bool use_hot = HOT;          // (a compile-time choice: with both mask paths in one kernel the register file spills)
-  const uint32_t qm8 = ((qm >> (8 * lh)) & 0xffu) & (lh ? 0x7fu : 0xffu);          // visible-bits of this lane's eight groups; slot 15 never
+  const uint32_t qm8 = attn_qm8(qm, lh);
   const float c2 = a.scale * 1.4426950408889634f;
   // row constants as accumulator start values: S - lse (log2 domain; lse = +inf marks a uniform row: P = 0) and dP - delta
   f32x16 neglse, negdel;
@@ -95,10 +84,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(mca_attn_bwd2_args 
   const u16* vbase = a.v + (int64_t)b * a.kv_bstride + h * DH;
   const uint8_t* kinfo_g = a.keyinfo + (int64_t)b * a.nk_pad;
   const u16* khot_g = use_hot ? a.khot + (int64_t)b * a.nk_pad * 16 : nullptr;
-  {
-    const uint8_t* flags_g = a.ktile_flags + (int64_t)b * a.n_ktiles64;
-    for (int i = tid; i < a.n_ktiles64; i += 256) flags_s[i] = flags_g[i];
-  }
+  attn_stage_flags(flags_s, a.ktile_flags + (int64_t)b * a.n_ktiles64, a.n_ktiles64, tid);
   __syncthreads();
 
   int srow[2], sc[2];
@@ -138,26 +124,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(mca_attn_bwd2_args 
 #pragma unroll
     for (int i = 0; i < 2; i++) {
       *reinterpret_cast<bf16x8*>(Ks + buf * AK * DH + rt_off(srow[i], sc[i])) = rk[i];          // rows for S, columns for dQ
-      *reinterpret_cast<bf16x8*>(Vs + buf * AK * DH + row_off(srow[i], sc[i])) = rv[i];
+      *reinterpret_cast<bf16x8*>(Vs + buf * AK * DH + k_off(srow[i], sc[i])) = rv[i];
     }
     if (use_hot) *reinterpret_cast<uint2*>(&hot_s[buf][tid * 4]) = rhot;
     else if (tid < 16) *reinterpret_cast<uint32_t*>(&kinfo[buf][tid * 4]) = rhot.x;
   };
 
   if (wave == 0) {
-    const int lb = a.q_ptr[qt], le = a.q_ptr[qt + 1];
-    int n = 0;
-    for (int i0 = lb; i0 < le; i0 += 64) {
-      const int i = i0 + lane;
-      const uint32_t e = i < le ? a.q_kt[i] : 0u;
-      const uint8_t fl = i < le ? flags_s[e & 0x7fffffffu] : (uint8_t)0;
-      const bool keep = fl != 0;
-      const unsigned long long m = __ballot(keep);
-      // bit 31 = no element-wise mask needed (structurally full AND every key of the tile valid in this sample)
-      if (keep) live_s[n + __popcll(m & ((1ull << lane) - 1ull))] = (e & 0x7fffffffu) | ((e >> 31) && fl == 2 ? 0x80000000u : 0u);
-      n += __popcll(m);
-    }
-    if (lane == 0) { n_live_s = n; live_s[n] = 0u; live_s[n + 1] = 0u; }
+    const int n = attn_compact_tiles<true>(a.q_ptr, a.q_kt, qt, flags_s, live_s, &n_live_s, lane);
+    if (lane == 0) { live_s[n] = 0u; live_s[n + 1] = 0u; }          // two sentinels: the loop reads two entries ahead
   }
   __syncthreads();
   const int it_end = n_live_s;
@@ -176,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(mca_attn_bwd2_args 
 #pragma unroll
     for (int st = 0; st < 4; st++) {
       kaddr[st] = kb_lds + 2u * (unsigned)rt_off(l31, 2 * st + lh);
-      vaddr[st] = vb_lds + 2u * (unsigned)row_off(l31, 2 * st + lh);
+      vaddr[st] = vb_lds + 2u * (unsigned)k_off(l31, 2 * st + lh);
     }
   }
   const int tq = (lane & 15) >> 2, tp = lane & 3, tg = (lane >> 4) & 1;
@@ -228,14 +203,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(mca_attn_bwd2_args 
 #undef DQ_DSREAD128
     }
     if (need_mask && use_hot) {          // blocked (query, key) pairs: -32768 on top of the score, exp2 is exactly 0
-      u32x4v qb;
-#pragma unroll
-      for (int w = 0; w < 4; w++)
-        qb[w] = (((qm8 >> (2 * w)) & 1u) ? 0u : 0xC700u) | (((qm8 >> (2 * w + 1)) & 1u) ? 0u : 0xC7000000u);
+      const bf16x8 qb = attn_qblk8(qm8);
 #pragma unroll
       for (int kb = 0; kb < 2; kb++) {
         const bf16x8 hf = *reinterpret_cast<const bf16x8*>(&hot_s[buf][(kb * 32 + l31) * 16 + 8 * lh]);
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(hf, *reinterpret_cast<const bf16x8*>(&qb), s[kb], 0, 0, 0);
+        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(hf, qb, s[kb], 0, 0, 0);
       }
     }
     if (!PRESCALED) {
@@ -365,20 +337,10 @@ __global__ __launch_bounds__(64 * W) void attn_bwd_dkv_kernel(mca_attn_bwd2_args
   float* dvm_s = reinterpret_cast<float*>(qlist + MAX_QTILES);    // [64]
   u16* qblk_s = reinterpret_cast<u16*>(dvm_s + DH);               // [2][64][16]: query side of the mask product
 
-  const int lin0 = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-  const int lin = (dbg & 16) ? lin0 : xcd_remap(lin0, (int)(gridDim.x * gridDim.y * gridDim.z));
-  const int4 w = reinterpret_cast<const int4*>(a.k_wg)[lin % (int)gridDim.x];
-  const int kbi = w.x, it_begin = w.y, first_qt = w.w;
-  const int h = (lin / (int)gridDim.x) % (int)gridDim.y, b = lin / (int)(gridDim.x * gridDim.y);
-  // a key block whose four 64-key tiles hold no valid key in this sample (ktile_flags == 0: a dropped modality) sweeps nothing:
+  const auto [kbi, it_begin, n_list, first_qt, h, b] = attn_kwg_decode(a.k_wg, dbg);
+  // a key block whose 64-key tiles hold no valid key in this sample (ktile_flags == 0: a dropped modality) sweeps nothing:
   // dK = 0, dV = dvmean straight from the epilogue
-  int n_it = w.z;
-  {
-    const uint8_t* fl = a.ktile_flags + (int64_t)b * a.n_ktiles64;
-    int live = 0;
-    for (int t = 0; t < BKEYS / AK; t++) { const int kt = kbi * (BKEYS / AK) + t; if (kt < a.n_ktiles64) live |= fl[kt]; }
-    if (!live) n_it = 0;
-  }
+  const int n_it = attn_kblock_live<BKEYS>(a.ktile_flags + (int64_t)b * a.n_ktiles64, a.n_ktiles64, kbi) ? n_list : 0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, lh = lane >> 5;
   const int key0 = kbi * BKEYS;

@@ -20,14 +20,9 @@
 //                          P is fed as 128 * 2^(S - m) (unit scale; the sum carries the same factor), e4m3 range down to
 //                          2^-16 of the row maximum.
 // The backward stays in bf16 (attention_bwd2.hip) with the log-sum-exp this forward wrote.
-#include "common.h"
+#include "attention_common.h"
 
-#define AQ 128
-#define AK 64
-#define DH 64
-#define MAX_KTILES 512
 typedef int v8i __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------------------
 // quantisation
@@ -140,16 +135,11 @@ __global__ __launch_bounds__(256) void attn_fwd8_kernel(mca_attn_fwd_args a, mca
   uint8_t* Ks = lds;
   uint8_t* Vs = lds + 2 * AK * DH;
 
-  const int lin0 = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-  const int lin = (dbg & 16) ? lin0 : xcd_remap(lin0, (int)(gridDim.x * gridDim.y * gridDim.z));
-  const int qt = a.q_order[lin % (int)gridDim.x];
-  const int h = (lin / (int)gridDim.x) % (int)gridDim.y, b = lin / (int)(gridDim.x * gridDim.y);
+  const auto [lin0, qt, h, b] = attn_wg_decode(a.q_order, dbg);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, lh = lane >> 5;
-  const int q0 = qt * AQ + wave * 32;
-  int qrow = q0 + l31;
-  const bool qvalid = qrow < a.nq;
-  if (qrow > a.nq - 1) qrow = a.nq - 1;
+  bool qvalid;
+  const int qrow = attn_qrow(qt, wave * 32 + l31, a.nq, qvalid);
   const int ntiles = f.n_ktiles;
   const int64_t bh = (int64_t)b * a.heads + h;
 
@@ -164,9 +154,9 @@ __global__ __launch_bounds__(256) void attn_fwd8_kernel(mca_attn_fwd_args a, mca
     qscale = f.qs[rowi * 2 + lh];
   }
   const uint32_t qm = a.qmask[qrow];
-  // the mask as a matrix product (mca_build_keyhot; a bf16 32x32x16 product into the same fp32 accumulators)
+  // the mask as a matrix product (attention_common.h; a bf16 32x32x16 product into the same fp32 accumulators)
   const bool use_hot = DMA || a.khot != nullptr;
-  bf16x8 qblk;
+  bf16x8 qblk;          // attn_qblk's lines, kept here: calling it moved two instructions inside this kernel's loop
 #pragma unroll
   for (int j = 0; j < 8; j++) {
     const int g = 8 * lh + j;
@@ -186,10 +176,7 @@ __global__ __launch_bounds__(256) void attn_fwd8_kernel(mca_attn_fwd_args a, mca
   const uint8_t* v8b = f.v8t + bh * (int64_t)ntiles * DH * AK;
   const uint8_t* vsb = f.vs + bh * (int64_t)ntiles * DH * 2;
   const uint8_t* kinfo_g = a.keyinfo + (int64_t)b * a.nk_pad;
-  {
-    const uint8_t* flags_g = a.ktile_flags + (int64_t)b * a.n_ktiles;
-    for (int i = tid; i < a.n_ktiles; i += 256) flags_s[i] = flags_g[i];
-  }
+  attn_stage_flags(flags_s, a.ktile_flags + (int64_t)b * a.n_ktiles, a.n_ktiles, tid);
   __syncthreads();
 
   // staging: a K8 / V8T tile is 4 KiB = 256 chunks of 16 B: one of each per thread; the 128 + 128 scale bytes and the 64 key
@@ -230,19 +217,7 @@ __global__ __launch_bounds__(256) void attn_fwd8_kernel(mca_attn_fwd_args a, mca
     }
   };
 
-  if (wave == 0) {
-    const int lb = a.q_ptr[qt], le = a.q_ptr[qt + 1];
-    int n = 0;
-    for (int i0 = lb; i0 < le; i0 += 64) {
-      const int i = i0 + lane;
-      const uint32_t e = i < le ? a.q_kt[i] : 0u;
-      const bool keep = i < le && flags_s[e & 0x7fffffffu] != 0;
-      const unsigned long long m = __ballot(keep);
-      if (keep) live_s[n + __popcll(m & ((1ull << lane) - 1ull))] = e;
-      n += __popcll(m);
-    }
-    if (lane == 0) n_live_s = n;
-  }
+  if (wave == 0) attn_compact_tiles<false>(a.q_ptr, a.q_kt, qt, flags_s, live_s, &n_live_s, lane);
   __syncthreads();
   const int it_end = n_live_s;
   int it = 0, buf = 0;
@@ -348,19 +323,7 @@ __global__ __launch_bounds__(256) void attn_fwd8_kernel(mca_attn_fwd_args a, mca
   const float inv = uniform ? 0.f : 1.f / l_run;
   if (qvalid) {
     if (lh == 0) a.lse[bh * a.nq + qrow] = uniform ? INFINITY : m_run + log2f(l_run) - 7.f;
-    u16* op = a.o + (int64_t)b * a.o_bstride + (int64_t)qrow * a.o_ld + h * DH;
-    const float* vm = a.vmean + (int64_t)b * a.heads * DH + h * DH;
-#pragma unroll
-    for (int n = 0; n < 2; n++)
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        const int d = n * 32 + 8 * g + 4 * lh;
-        float v0, v1, v2, v3;
-        if (uniform) { v0 = vm[d]; v1 = vm[d + 1]; v2 = vm[d + 2]; v3 = vm[d + 3]; }
-        else { v0 = o[n][4 * g] * inv; v1 = o[n][4 * g + 1] * inv; v2 = o[n][4 * g + 2] * inv; v3 = o[n][4 * g + 3] * inv; }
-        uint2 pk; pk.x = pack2bf(v0, v1); pk.y = pack2bf(v2, v3);
-        *reinterpret_cast<uint2*>(op + d) = pk;
-      }
+    attn_store_o(a.o + (int64_t)b * a.o_bstride + (int64_t)qrow * a.o_ld + h * DH, a.vmean + (int64_t)b * a.heads * DH + h * DH, o, inv, uniform, lh);
   }
 }
 
@@ -472,16 +435,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq8_kernel(mca_attn_bwd2_args
   uint8_t* K8s = t8_s;
   uint8_t* V8s = t8_s + 2 * AK * DH;
 
-  const int lin0 = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-  const int lin = (dbg & 16) ? lin0 : xcd_remap(lin0, (int)(gridDim.x * gridDim.y * gridDim.z));
-  const int qt = a.q_order[lin % (int)gridDim.x];
-  const int h = (lin / (int)gridDim.x) % (int)gridDim.y, b = lin / (int)(gridDim.x * gridDim.y);
+  const auto [lin0, qt, h, b] = attn_wg_decode(a.q_order, dbg);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, lh = lane >> 5;
-  const int q0 = qt * AQ + wave * 32;
-  int qrow = q0 + l31;
-  const bool qvalid = qrow < a.nq;
-  if (qrow > a.nq - 1) qrow = a.nq - 1;
+  bool qvalid;
+  const int qrow = attn_qrow(qt, wave * 32 + l31, a.nq, qvalid);
   const int ntiles = f.n_ktiles;
   const int64_t bh = (int64_t)b * a.heads + h;
 
@@ -498,7 +456,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq8_kernel(mca_attn_bwd2_args
     doscale = f.dos[rowi * 2 + lh];
   }
   const uint32_t qm = a.qmask[qrow];
-  const uint32_t qm8 = ((qm >> (8 * lh)) & 0xffu) & (lh ? 0x7fu : 0xffu);
+  const uint32_t qm8 = attn_qm8(qm, lh);
   f32x16 neglse, negdel;
   {
     const int64_t ri = bh * a.nq + qrow;
@@ -518,10 +476,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq8_kernel(mca_attn_bwd2_args
   const uint8_t* v8b = f.v8 + bh * ((int64_t)ntiles * AK) * DH;
   const uint8_t* vsb = f.vs + bh * ((int64_t)ntiles * AK) * 2;
   const u16* khot_g = a.khot + (int64_t)b * a.nk_pad * 16;
-  {
-    const uint8_t* flags_g = a.ktile_flags + (int64_t)b * a.n_ktiles64;
-    for (int i = tid; i < a.n_ktiles64; i += 256) flags_s[i] = flags_g[i];
-  }
+  attn_stage_flags(flags_s, a.ktile_flags + (int64_t)b * a.n_ktiles64, a.n_ktiles64, tid);
   __syncthreads();
 
   // staging: the bf16 K tile (512 pieces of 16 bytes), K8 and V8 (256 each), the 256 scale bytes and the one-hot tile (128 pieces)
@@ -559,7 +514,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq8_kernel(mca_attn_bwd2_args
     }
   };
 
-  if (wave == 0) {
+  if (wave == 0) {          // attn_compact_tiles<true>'s lines, kept here: calling it re-allocated this kernel's registers, its loop included
     const int lb = a.q_ptr[qt], le = a.q_ptr[qt + 1];
     int n = 0;
     for (int i0 = lb; i0 < le; i0 += 64) {
@@ -602,14 +557,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq8_kernel(mca_attn_bwd2_args
       dp[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(vf, dof, negdel, 0, 0, 0, vscale, 0, doscale);
     }
     if (need_mask) {          // blocked (query, key) pairs: -32768 on top of the score, exp2 is exactly 0
-      u32x4v qb;
-#pragma unroll
-      for (int w = 0; w < 4; w++)
-        qb[w] = (((qm8 >> (2 * w)) & 1u) ? 0u : 0xC700u) | (((qm8 >> (2 * w + 1)) & 1u) ? 0u : 0xC7000000u);
+      const bf16x8 qb = attn_qblk8(qm8);
 #pragma unroll
       for (int kb = 0; kb < 2; kb++) {
         const bf16x8 hf = *reinterpret_cast<const bf16x8*>(&hot_s[buf][(kb * 32 + l31) * 16 + 8 * lh]);
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(hf, *reinterpret_cast<const bf16x8*>(&qb), s[kb], 0, 0, 0);
+        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(hf, qb, s[kb], 0, 0, 0);
       }
     }
     // dS^T = P^T o (dP^T - delta), packed as the B operand of the dQ^T product (bf16)
@@ -714,18 +666,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv8_kernel(mca_attn_bwd2_args a
   float* dvm_s = reinterpret_cast<float*>(qlist + MAX_QTILES8);
   u16* qblk_s = reinterpret_cast<u16*>(dvm_s + DH);                   // [2][64][16]
 
-  const int lin0 = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-  const int lin = (dbg & 16) ? lin0 : xcd_remap(lin0, (int)(gridDim.x * gridDim.y * gridDim.z));
-  const int4 w = reinterpret_cast<const int4*>(a.k_wg)[lin % (int)gridDim.x];
-  const int kbi = w.x, it_begin = w.y, first_qt = w.w;
-  const int h = (lin / (int)gridDim.x) % (int)gridDim.y, b = lin / (int)(gridDim.x * gridDim.y);
-  int n_it = w.z;
-  {
-    const uint8_t* fl = a.ktile_flags + (int64_t)b * a.n_ktiles64;
-    int live = 0;
-    for (int t = 0; t < BKEYS / AK; t++) { const int kt = kbi * (BKEYS / AK) + t; if (kt < a.n_ktiles64) live |= fl[kt]; }
-    if (!live) n_it = 0;
-  }
+  const auto [kbi, it_begin, n_list, first_qt, h, b] = attn_kwg_decode(a.k_wg, dbg);
+  const int n_it = attn_kblock_live<BKEYS>(a.ktile_flags + (int64_t)b * a.n_ktiles64, a.n_ktiles64, kbi) ? n_list : 0;          // (attn_bwd_dkv_kernel)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, lh = lane >> 5;
   const int key0 = kbi * BKEYS;

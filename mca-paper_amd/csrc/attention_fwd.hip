@@ -16,13 +16,7 @@
 // Semantics kept from the reference: a query row with no allowed, un-padded key gets a UNIFORM
 // distribution over ALL nk keys (softmax of a constant row), i.e. its output is the mean of V; such rows
 // are marked with lse = +inf for the backward.
-#include "common.h"
-
-#define AQ 128      // query rows per workgroup
-#define AK 64       // keys per tile
-#define DH 64       // head dim (fixed)
-#define MAX_KTILES 512
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
+#include "attention_common.h"
 
 MCA_TRACE_BUFFER(attn_fwd)      // knob 8 = 8: s_memtime stamps of one wavefront (tools/trace_attn_fwd.py)
 #ifdef MCA_TRACE_BUILD      // the stamps pin the instruction order, so the production build carries none (build.py: trace=True)
@@ -31,9 +25,7 @@ MCA_TRACE_BUFFER(attn_fwd)      // knob 8 = 8: s_memtime stamps of one wavefront
 #define FW_STAMP() do { } while (0)
 #endif
 
-// K tile image: [64 keys][64 d] bf16, 128-byte rows, chunk c (16 B) of row r at c ^ ((r>>1)&7)
-__device__ __forceinline__ int k_off(int r, int c) { return r * 64 + ((c ^ ((r >> 1) & 7)) << 3); }
-// V tile image: same shape, chunk c of row r at c ^ (4*((r>>1)&1)): the 4 rows of a transposed 4x16 read
+// V tile image: the K image's shape (k_off, attention_common.h), chunk c of row r at c ^ (4*((r>>1)&1)): the 4 rows of a transposed 4x16 read
 // fall into 4 distinct 64-byte bank quarters
 __device__ __forceinline__ int v_off(int r, int c) { return r * 64 + ((c ^ (((r >> 1) & 1) << 2)) << 3); }
 
@@ -43,44 +35,22 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(mca_attn_fwd_args a, int 
   __shared__ __attribute__((aligned(16))) uint8_t kinfo[2][AK];
   __shared__ __attribute__((aligned(16))) u16 hot_s[2][AK * 16];   // one-hot key groups of the tile (mask product operand)
   __shared__ uint8_t flags_s[MAX_KTILES];       // this sample's key-tile flags
-  // This query tile's list entries whose key tile has at least one valid key in this sample, compacted once: reading the
-  // CSR entry and the flag of the NEXT live tile at the top of every iteration was a chain of a scalar global load and an
-  // LDS read in front of the K / V loads (most of the 1,500 cycles the traced "S" phase took).
-  __shared__ uint32_t live_s[MAX_KTILES];
+  __shared__ uint32_t live_s[MAX_KTILES];       // this query tile's live key tiles (attn_compact_tiles)
   __shared__ int n_live_s;
   u16* Ks = lds;
   u16* Vs = lds + 2 * AK * DH;
 
-  // XCD-aware order: the query tiles of one (sample, head) read the same K / V, so they are given to one XCD (in launch
-  // order they were dealt round all eight and every L2 fetched every K / V: 1,128 MB per launch against 250 MB)
-  const int lin0 = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-  const int lin = (dbg & 16) ? lin0 : xcd_remap(lin0, (int)(gridDim.x * gridDim.y * gridDim.z));          // knob 9 = 16: launch order (A/B)
-  const int qt = a.q_order[lin % (int)gridDim.x];
-  const int h = (lin / (int)gridDim.x) % (int)gridDim.y, b = lin / (int)(gridDim.x * gridDim.y);
+  const auto [lin0, qt, h, b] = attn_wg_decode(a.q_order, dbg);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, lh = lane >> 5;
-  const int q0 = qt * AQ + wave * 32;
-  int qrow = q0 + l31;
-  const bool qvalid = qrow < a.nq;
-  if (qrow > a.nq - 1) qrow = a.nq - 1;
+  bool qvalid;
+  const int qrow = attn_qrow(qt, wave * 32 + l31, a.nq, qvalid);
 
-  // Q fragments (B operand): lane holds Q[q][16s + 8*lh + j]
   bf16x8 qf[4];
-  {
-    const u16* qp = a.q + (int64_t)b * a.q_bstride + (int64_t)qrow * a.q_ld + h * DH + 8 * lh;
-#pragma unroll
-    for (int s = 0; s < 4; s++) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
-  }
+  attn_load_qf(qf, a.q + (int64_t)b * a.q_bstride + (int64_t)qrow * a.q_ld + h * DH, lh);
   const uint32_t qm = a.qmask[qrow];
-  // the mask as a matrix product (mca_build_keyhot): Qblk[q][g] = group g visible ? 0 : -32768 (bf16 0xC700), slot 15 (padded
-  // keys) always -32768; this lane holds groups 8 lh .. 8 lh + 7 of its query
-  const bool use_hot = a.khot != nullptr;
-  bf16x8 qblk;
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    const int g = 8 * lh + j;
-    qblk[j] = (g < 15 && ((qm >> g) & 1u)) ? (short)0 : (short)0xC700;
-  }
+  const bool use_hot = a.khot != nullptr;          // the mask as a matrix product (attention_common.h)
+  const bf16x8 qblk = attn_qblk(qm, lh);
   // scores -> log2 domain; q pre-scaled by scale * log2(e) (MCA_ATTN_Q_PRESCALED): they already are
   const float c2 = PRESCALED ? 1.f : a.scale * 1.4426950408889634f;
 
@@ -95,10 +65,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(mca_attn_fwd_args a, int 
   const u16* vbase = a.v + (int64_t)b * a.kv_bstride + h * DH;
   const uint8_t* kinfo_g = a.keyinfo + (int64_t)b * a.nk_pad;
   const u16* khot_g = use_hot ? a.khot + (int64_t)b * a.nk_pad * 16 : nullptr;
-  {
-    const uint8_t* flags_g = a.ktile_flags + (int64_t)b * a.n_ktiles;
-    for (int i = tid; i < a.n_ktiles; i += 256) flags_s[i] = flags_g[i];
-  }
+  attn_stage_flags(flags_s, a.ktile_flags + (int64_t)b * a.n_ktiles, a.n_ktiles, tid);
   __syncthreads();
 
   // staging: 512 chunks of 16 B per tile per operand, 2 per thread.  The per-lane element offset inside a tile is
@@ -146,20 +113,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(mca_attn_fwd_args a, int 
     else if (tid < 16) *reinterpret_cast<uint32_t*>(&kinfo[buf][tid * 4]) = rinfo;
   };
 
-  // the tile list of this query tile, minus tiles whose keys are all padded in this sample (wavefront 0 compacts it)
-  if (wave == 0) {
-    const int lb = a.q_ptr[qt], le = a.q_ptr[qt + 1];
-    int n = 0;
-    for (int i0 = lb; i0 < le; i0 += 64) {
-      const int i = i0 + lane;
-      const uint32_t e = i < le ? a.q_kt[i] : 0u;
-      const bool keep = i < le && flags_s[e & 0x7fffffffu] != 0;
-      const unsigned long long m = __ballot(keep);
-      if (keep) live_s[n + __popcll(m & ((1ull << lane) - 1ull))] = e;
-      n += __popcll(m);
-    }
-    if (lane == 0) n_live_s = n;
-  }
+  if (wave == 0) attn_compact_tiles<false>(a.q_ptr, a.q_kt, qt, flags_s, live_s, &n_live_s, lane);
   __syncthreads();
   const int it_end = n_live_s;
   int it = 0;
@@ -286,19 +240,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(mca_attn_fwd_args a, int 
   const float inv = uniform ? 0.f : 1.f / l_run;
   if (qvalid) {
     if (lh == 0) a.lse[((int64_t)b * a.heads + h) * a.nq + qrow] = uniform ? INFINITY : m_run + log2f(l_run);
-    u16* op = a.o + (int64_t)b * a.o_bstride + (int64_t)qrow * a.o_ld + h * DH;
-    const float* vm = a.vmean + (int64_t)b * a.heads * DH + h * DH;
-#pragma unroll
-    for (int n = 0; n < 2; n++)
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        const int d = n * 32 + 8 * g + 4 * lh;
-        float v0, v1, v2, v3;
-        if (uniform) { v0 = vm[d]; v1 = vm[d + 1]; v2 = vm[d + 2]; v3 = vm[d + 3]; }
-        else { v0 = o[n][4 * g] * inv; v1 = o[n][4 * g + 1] * inv; v2 = o[n][4 * g + 2] * inv; v3 = o[n][4 * g + 3] * inv; }
-        uint2 pk; pk.x = pack2bf(v0, v1); pk.y = pack2bf(v2, v3);
-        *reinterpret_cast<uint2*>(op + d) = pk;
-      }
+    attn_store_o(a.o + (int64_t)b * a.o_bstride + (int64_t)qrow * a.o_ld + h * DH, a.vmean + (int64_t)b * a.heads * DH + h * DH, o, inv, uniform, lh);
   }
 }
 
@@ -335,25 +277,16 @@ __global__ __launch_bounds__(256, LAZY ? 3 : 4) void attn_fwd4_kernel(mca_attn_f
   u16* Vs = lds + 2 * AK * DH;
   u16* Hs = lds + 4 * AK * DH;
 
-  const int lin0 = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-  const int lin = (dbg & 16) ? lin0 : xcd_remap(lin0, (int)(gridDim.x * gridDim.y * gridDim.z));
-  const int qt = a.q_order[lin % (int)gridDim.x];
-  const int h = (lin / (int)gridDim.x) % (int)gridDim.y, b = lin / (int)(gridDim.x * gridDim.y);
+  const auto [lin0, qt, h, b] = attn_wg_decode(a.q_order, dbg);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
-  const int q0 = qt * AQ + wave * 32;
-  int qrow = q0 + l31;
-  const bool qvalid = qrow < a.nq;
-  if (qrow > a.nq - 1) qrow = a.nq - 1;
+  bool qvalid;
+  const int qrow = attn_qrow(qt, wave * 32 + l31, a.nq, qvalid);
 
   bf16x8 qf[4];
-  {
-    const u16* qp = a.q + (int64_t)b * a.q_bstride + (int64_t)qrow * a.q_ld + h * DH + 8 * lh;
-#pragma unroll
-    for (int s = 0; s < 4; s++) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
-  }
+  attn_load_qf(qf, a.q + (int64_t)b * a.q_bstride + (int64_t)qrow * a.q_ld + h * DH, lh);
   const uint32_t qm = a.qmask[qrow];
-  const uint32_t qm8 = ((qm >> (8 * lh)) & 0xffu) & (lh ? 0x7fu : 0xffu);
+  const uint32_t qm8 = attn_qm8(qm, lh);
 
   f32x16 o[2];
 #pragma unroll
@@ -372,10 +305,7 @@ __global__ __launch_bounds__(256, LAZY ? 3 : 4) void attn_fwd4_kernel(mca_attn_f
   const u16* kbase = a.k + (int64_t)b * a.kv_bstride + h * DH;
   const u16* vbase = a.v + (int64_t)b * a.kv_bstride + h * DH;
   const u16* khot_g = a.khot + (int64_t)b * a.nk_pad * 16;
-  {
-    const uint8_t* flags_g = a.ktile_flags + (int64_t)b * a.n_ktiles;
-    for (int i = tid; i < a.n_ktiles; i += 256) flags_s[i] = flags_g[i];
-  }
+  attn_stage_flags(flags_s, a.ktile_flags + (int64_t)b * a.n_ktiles, a.n_ktiles, tid);
   __syncthreads();
 
   // DMA pieces: piece p = 256 i + tid of a tile image lands at byte 16 p; it must hold chunk c = slot ^ swizzle(row) of row
@@ -386,7 +316,7 @@ __global__ __launch_bounds__(256, LAZY ? 3 : 4) void attn_fwd4_kernel(mca_attn_f
   for (int i = 0; i < 2; i++) {
     const int p = 256 * i + tid, r = p >> 3, sl = p & 7;
     prow[i] = r;
-    koff[i] = (unsigned)(r * (int)a.kv_ld + ((sl ^ ((r >> 1) & 7)) << 3));
+    koff[i] = (unsigned)(r * (int)a.kv_ld + k_swz(r, sl));
     voff[i] = (unsigned)(r * (int)a.kv_ld + ((sl ^ (((r >> 1) & 1) << 2)) << 3));
   }
   const int last_kt = a.n_ktiles - 1;
@@ -412,20 +342,7 @@ __global__ __launch_bounds__(256, LAZY ? 3 : 4) void attn_fwd4_kernel(mca_attn_f
     }
   };
 
-  if (wave == 0) {
-    const int lb = a.q_ptr[qt], le = a.q_ptr[qt + 1];
-    int n = 0;
-    for (int i0 = lb; i0 < le; i0 += 64) {
-      const int i = i0 + lane;
-      const uint32_t e = i < le ? a.q_kt[i] : 0u;
-      const uint8_t fl = i < le ? flags_s[e & 0x7fffffffu] : (uint8_t)0;
-      const bool keep = fl != 0;
-      const unsigned long long m = __ballot(keep);
-      if (keep) live_s[n + __popcll(m & ((1ull << lane) - 1ull))] = (e & 0x7fffffffu) | (((e >> 31) && fl == 2) ? 0x80000000u : 0u);
-      n += __popcll(m);
-    }
-    if (lane == 0) n_live_s = n;
-  }
+  if (wave == 0) attn_compact_tiles<true>(a.q_ptr, a.q_kt, qt, flags_s, live_s, &n_live_s, lane);
   __syncthreads();
   const int it_end = n_live_s;
   int buf = 0;
@@ -454,14 +371,11 @@ __global__ __launch_bounds__(256, LAZY ? 3 : 4) void attn_fwd4_kernel(mca_attn_f
       }
     }
     if (need_mask) {
-      u32x4v qb;
-#pragma unroll
-      for (int w = 0; w < 4; w++)
-        qb[w] = (((qm8 >> (2 * w)) & 1u) ? 0u : 0xC700u) | (((qm8 >> (2 * w + 1)) & 1u) ? 0u : 0xC7000000u);
+      const bf16x8 qb = attn_qblk8(qm8);
 #pragma unroll
       for (int kb = 0; kb < 2; kb++) {
         const bf16x8 hf = *reinterpret_cast<const bf16x8*>(Hs + buf * AK * 16 + (kb * 32 + l31) * 16 + 8 * lh);
-        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(hf, *reinterpret_cast<const bf16x8*>(&qb), s[kb], 0, 0, 0);
+        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(hf, qb, s[kb], 0, 0, 0);
       }
     }
     float rs = 0.f;
@@ -564,19 +478,7 @@ __global__ __launch_bounds__(256, LAZY ? 3 : 4) void attn_fwd4_kernel(mca_attn_f
   const float inv = uniform ? 0.f : 1.f / l_tot;
   if (qvalid) {
     if (lh == 0) a.lse[((int64_t)b * a.heads + h) * a.nq + qrow] = uniform ? INFINITY : m_run + log2f(l_tot);
-    u16* op = a.o + (int64_t)b * a.o_bstride + (int64_t)qrow * a.o_ld + h * DH;
-    const float* vm = a.vmean + (int64_t)b * a.heads * DH + h * DH;
-#pragma unroll
-    for (int n = 0; n < 2; n++)
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        const int d = n * 32 + 8 * g + 4 * lh;
-        float v0, v1, v2, v3;
-        if (uniform) { v0 = vm[d]; v1 = vm[d + 1]; v2 = vm[d + 2]; v3 = vm[d + 3]; }
-        else { v0 = o[n][4 * g] * inv; v1 = o[n][4 * g + 1] * inv; v2 = o[n][4 * g + 2] * inv; v3 = o[n][4 * g + 3] * inv; }
-        uint2 pk; pk.x = pack2bf(v0, v1); pk.y = pack2bf(v2, v3);
-        *reinterpret_cast<uint2*>(op + d) = pk;
-      }
+    attn_store_o(a.o + (int64_t)b * a.o_bstride + (int64_t)qrow * a.o_ld + h * DH, a.vmean + (int64_t)b * a.heads * DH + h * DH, o, inv, uniform, lh);
   }
 }
 

@@ -16,17 +16,10 @@
 //
 // A row the forward marked uniform (lse = +inf: no allowed, un-padded key; the reference's softmax of a constant row) gets the
 // host's uniform_mass (key count of the group / nk) and 1 / nk for every key, padded and blocked ones included.
-#include "common.h"
+#include "attention_common.h"
 
-#define AQ 128      // query rows per workgroup
-#define AK 64       // keys per tile
-#define DH 64       // head dim (fixed)
-#define MAX_KTILES 512
 #define ACC_LD 33   // row stride of the group accumulators: 32 groups (31 = padded keys, never read back) + 1 (LDS banks)
 #define MIXED 255u  // a 32-key block with more than one group
-
-// K tile image: [64 keys][64 d] bf16, 128-byte rows, chunk c (16 B) of row r at c ^ ((r>>1)&7) (as the forward stages it)
-__device__ __forceinline__ int rk_off(int r, int c) { return r * 64 + ((c ^ ((r >> 1) & 7)) << 3); }
 
 __global__ __launch_bounds__(256, 4) void attn_readout_kernel(mca_attn_readout_args a, float inv_nk) {
   __shared__ __attribute__((aligned(16))) u16 Ks[2 * AK * DH];          // K double-buffered: 16 KiB
@@ -38,24 +31,15 @@ __global__ __launch_bounds__(256, 4) void attn_readout_kernel(mca_attn_readout_a
   __shared__ uint8_t uni_s[AQ];
   __shared__ int n_live_s;
 
-  const int lin0 = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-  const int lin = xcd_remap(lin0, (int)(gridDim.x * gridDim.y * gridDim.z));          // the query tiles of a (sample, head) share an L2
-  const int qt = a.q_order[lin % (int)gridDim.x];
-  const int h = (lin / (int)gridDim.x) % (int)gridDim.y, b = lin / (int)(gridDim.x * gridDim.y);
+  const auto [lin0, qt, h, b] = attn_wg_decode(a.q_order, 0);          // (no knob: always the XCD-aware order)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, lh = lane >> 5;
   const int arow = wave * 32 + l31;          // row inside the tile
-  int qrow = qt * AQ + arow;
-  const bool qvalid = qrow < a.nq;
-  if (qrow > a.nq - 1) qrow = a.nq - 1;
+  bool qvalid;
+  const int qrow = attn_qrow(qt, arow, a.nq, qvalid);
 
-  // Q fragments (B operand): lane holds Q[q][16s + 8*lh + j]
   bf16x8 qf[4];
-  {
-    const u16* qp = a.q + (int64_t)b * a.q_bstride + (int64_t)qrow * a.q_ld + h * DH + 8 * lh;
-#pragma unroll
-    for (int s = 0; s < 4; s++) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
-  }
+  attn_load_qf(qf, a.q + (int64_t)b * a.q_bstride + (int64_t)qrow * a.q_ld + h * DH, lh);
   const uint32_t qm = a.qmask[qrow];
   const float lse = a.lse[((int64_t)b * a.heads + h) * a.nq + qrow];
   const bool uniform = lse == INFINITY;
@@ -107,11 +91,12 @@ __global__ __launch_bounds__(256, 4) void attn_readout_kernel(mca_attn_readout_a
   };
   auto swrite = [&](int buf) {
 #pragma unroll
-    for (int i = 0; i < 2; i++) *reinterpret_cast<bf16x8*>(Ks + buf * AK * DH + rk_off(srow[i], sc[i])) = rk[i];
+    for (int i = 0; i < 2; i++) *reinterpret_cast<bf16x8*>(Ks + buf * AK * DH + k_off(srow[i], sc[i])) = rk[i];
     if (tid < 16) *reinterpret_cast<uint32_t*>(&kinfo[buf][tid * 4]) = rinfo;
   };
 
-  // the tile list of this query tile, minus tiles whose keys are all padded in this sample (wavefront 0 compacts it)
+  // the tile list of this query tile, minus tiles whose keys are all padded in this sample (wavefront 0 compacts it).  Not
+  // attn_compact_tiles: this one drops bit 31, bounds every entry and position, and marks the tiles it keeps in seen_s
   if (wave == 0) {
     const int lb = a.q_ptr[qt], le = a.q_ptr[qt + 1];
     int n = 0;
@@ -177,7 +162,7 @@ __global__ __launch_bounds__(256, 4) void attn_readout_kernel(mca_attn_readout_a
       for (int r = 0; r < 16; r++) s[r] = 0.f;
 #pragma unroll
       for (int st = 0; st < 4; st++) {
-        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(ks + rk_off(kb * 32 + l31, 2 * st + lh));
+        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(ks + k_off(kb * 32 + l31, 2 * st + lh));
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[st], s, 0, 0, 0);
       }
       float p[16];
