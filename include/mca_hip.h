@@ -519,6 +519,22 @@ int mca_rows_normalize_f32(const float* x, int64_t ldx, float* y, int64_t ldy, i
  * fmaf chain as the tile.  Every qidx[r] must be a row of q and < nt (the caller checks).  Integer atomics only.           */
 int mca_cosine_rank_f32(const float* q, int64_t ldq, const int32_t* qidx, int64_t nq, const float* t, int64_t ldt, int64_t nt,
                         int64_t d, float* s_true, int32_t* rank, mca_stream_t stream);
+/* Top-k retrieval over the same scores.  s[r][j] = q[i].t[j], i = qidx[r] (or r when qidx is NULL): the tile's fmaf chain,
+ * bitwise the value the rank kernel compares and the probe layer (act 0, no bias) stores.  The candidates of query r are the
+ * targets j < nt with tvalid[j] != 0 (tvalid may be NULL: all), j != exclude[r] (exclude may be NULL; -1 excludes nothing)
+ * and a score that is not NaN.  j comes before j' when s[r][j] > s[r][j'], or when the two compare equal (+0 and -0 do) and
+ * j < j': a total order, so the result depends on no tile, arrival or chunk order.  For c < k, score[r * lds + c] and
+ * index[r * ldi + c] are the c-th candidate in that order; columns past the number of candidates hold -inf and -1; nothing
+ * else is stored.  nq == 0: nothing launched; nt == 0: every row is padding.  The (nq, nt) matrix is never stored; ws holds
+ * the k best of every 1024-target chunk.  Integer LDS atomics only: two launches give the same bytes.
+ * MCA_E_BADARG (nothing launched): k < 1, d < 1, negative sizes, ldq / ldt < d, lds / ldi < k, a NULL q, t (nt > 0), score or
+ * index, a ws that is NULL or below the workspace query.  MCA_E_UNSUPPORTED: k > MCA_TOPK_MAX, nt > 65535 * 1024.          */
+#define MCA_TOPK_MAX 64
+/* bytes of workspace for a problem; host only, nothing launched; < 0 for an invalid problem (a size < 0, k outside 1..64) */
+int64_t mca_cosine_topk_workspace(int64_t nq, int64_t nt, int k);
+int mca_cosine_topk_f32(const float* q, int64_t ldq, const int32_t* qidx, int64_t nq, const float* t, int64_t ldt, int64_t nt,
+                        int64_t d, const uint8_t* tvalid, const int32_t* exclude, int k, void* ws, int64_t ws_bytes,
+                        float* score, int64_t lds, int32_t* index, int64_t ldi, mca_stream_t stream);
 /* doubles of workspace mca_pair_gauss_sum_f32 needs for n rows */
 int64_t mca_pair_gauss_workspace(int64_t n);
 /* sum_out[0] = sum_{i<j} exp(-t * ||x_i - x_j||^2) (exp in fp32, the squared distance a direct-difference fmaf chain, fp64

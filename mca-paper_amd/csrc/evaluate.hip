@@ -133,6 +133,161 @@ __global__ __launch_bounds__(256) void rank_count_kernel(const float* __restrict
   if (tid < TILE && m0 + tid < nq && cnt_s[tid]) atomicAdd(&rank[m0 + tid], cnt_s[tid]);
 }
 
+// ---- top-k: the k best (score, index) pairs per query under ONE total order, so no result depends on the order of arrival
+// a comes before b: the higher score, or on equal scores (+0 == -0) the lower index.  NaN never enters (filtered before).
+__device__ __forceinline__ bool topk_before(float sa, int ia, float sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
+
+// grid (query tiles, target chunks), the rank kernel's shape.  LDS: per query row the chunk's best k pairs so far, sorted
+// (dynamic: 64 * k * 8 bytes), and the survivors of the current tile as a 64 x 64 score image plus a 64-bit column mask per row
+// (set with integer atomicOr).  After each tile a thread offers those of its 4 x 4 outputs that are candidates and come before
+// the row's k-th entry; then each wave merges, row by row, the survivors into its 16 rows' lists: every element's place in the
+// merged list is the number of elements before it, counted with wave broadcasts of a loop bounded by k + 64.  Every barrier is
+// reached by the whole workgroup: the tile count is fixed at entry, the merge loops are per wave and hold no barrier.
+// The chunk's lists go to ws_s / ws_i [chunk][query][k], padded with -inf / -1.
+__global__ __launch_bounds__(256) void topk_chunk_kernel(const float* __restrict__ q, int64_t ldq, const int32_t* __restrict__ qidx, int64_t nq,
+                                                         const float* __restrict__ t, int64_t ldt, int64_t nt, int64_t d,
+                                                         const uint8_t* __restrict__ tvalid, const int32_t* __restrict__ exclude, int k,
+                                                         int tiles_per_chunk, float* __restrict__ ws_s, int32_t* __restrict__ ws_i) {
+  __shared__ float As[KC][LDSW], Bs[KC][LDSW];
+  __shared__ float cand[TILE][TILE];
+  __shared__ unsigned int cmask[TILE][2];
+  __shared__ int cnt_s[TILE];
+  extern __shared__ float best_dyn[];
+  float* best_s = best_dyn;
+  int* best_i = reinterpret_cast<int*>(best_dyn + TILE * k);
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, lane = tid & 63, wv = tid >> 6;
+  const int64_t m0 = (int64_t)blockIdx.x * TILE;
+  const int64_t ntiles = (nt + TILE - 1) / TILE, tile0 = (int64_t)blockIdx.y * tiles_per_chunk;
+  const int tiles = (int)(ntiles - tile0 < tiles_per_chunk ? ntiles - tile0 : tiles_per_chunk);
+  int ex[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) ex[i] = (exclude && m0 + ty * 4 + i < nq) ? exclude[m0 + ty * 4 + i] : -1;
+  if (tid < TILE) {
+    cnt_s[tid] = 0;
+    cmask[tid][0] = 0u;
+    cmask[tid][1] = 0u;
+  }
+  for (int tt = 0; tt < tiles; tt++) {
+    const int64_t n0 = (tile0 + tt) * TILE;
+    float acc[4][4];
+    zero_acc(acc);
+    tile_core<false, false>(acc, q, ldq, qidx, nq, m0, t, ldt, nullptr, nt, n0, 0, d, -1, As, Bs);          // d >= 1: ends with a barrier
+    bool ok[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int64_t n = n0 + tx * 4 + j;
+      ok[j] = n < nt && (!tvalid || tvalid[n] != 0);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int r = ty * 4 + i;
+      if (m0 + r >= nq) continue;
+      const bool full = cnt_s[r] == k;
+      const float ks = full ? best_s[r * k + k - 1] : 0.f;
+      const int ki = full ? best_i[r * k + k - 1] : 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int c = tx * 4 + j, n = (int)n0 + c;
+        const float s = acc[i][j];
+        if (ok[j] && n != ex[i] && s == s && (!full || topk_before(s, n, ks, ki))) {
+          cand[r][c] = s;
+          atomicOr(&cmask[r][c >> 5], 1u << (c & 31));
+        }
+      }
+    }
+    __syncthreads();
+    for (int rr = 0; rr < TILE / 4; rr++) {
+      const int r = wv * (TILE / 4) + rr;
+      const uint32_t mlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)cmask[r][0]), mhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)cmask[r][1]);
+      const uint64_t m = ((uint64_t)mhi << 32) | (uint64_t)mlo;
+      if (m == 0) continue;
+      const int n = __builtin_amdgcn_readfirstlane(cnt_s[r]);
+      const bool has_l = lane < n, has_c = (m >> lane) & 1;
+      const float ls = has_l ? best_s[r * k + lane] : 0.f, cs = has_c ? cand[r][lane] : 0.f;
+      const int li = has_l ? best_i[r * k + lane] : 0, ci = (int)n0 + lane;
+      int pos_l = lane, pos_c = 0;
+      for (uint64_t mm = m; mm; mm &= mm - 1) {          // at most 64 survivors
+        const int b = __builtin_ctzll(mm);
+        const float xs = __shfl(cs, b, WAVE);
+        const int xi = (int)n0 + b;
+        pos_l += topk_before(xs, xi, ls, li) ? 1 : 0;
+        pos_c += (b != lane && topk_before(xs, xi, cs, ci)) ? 1 : 0;
+      }
+      for (int e = 0; e < n; e++) {                      // n <= k
+        const float ys = __shfl(ls, e, WAVE);
+        const int yi = __shfl(li, e, WAVE);
+        pos_c += topk_before(ys, yi, cs, ci) ? 1 : 0;
+      }
+      // every lane has read its own entry above; a wave's LDS accesses complete in program order
+      if (has_l && pos_l < k) {
+        best_s[r * k + pos_l] = ls;
+        best_i[r * k + pos_l] = li;
+      }
+      if (has_c && pos_c < k) {
+        best_s[r * k + pos_c] = cs;
+        best_i[r * k + pos_c] = ci;
+      }
+      if (lane == 0) {
+        const int total = n + __builtin_popcountll(m);
+        cnt_s[r] = total < k ? total : k;
+        cmask[r][0] = 0u;
+        cmask[r][1] = 0u;
+      }
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < TILE * k; e += 256) {
+    const int r = e / k, c = e - r * k;
+    if (m0 + r >= nq) break;
+    const int64_t off = ((int64_t)blockIdx.y * nq + m0 + r) * k + c;
+    const bool have = c < cnt_s[r];
+    ws_s[off] = have ? best_s[e] : -__builtin_inff();
+    ws_i[off] = have ? best_i[e] : -1;
+  }
+}
+
+// one wave per query: the chunks' lists, each sorted and padded, merged one after the other into the wave's running list by
+// the same counting (lane l holds entry l); a 64-entry LDS row per wave moves the entries to their places.  No block barrier.
+__global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict__ ws_s, const int32_t* __restrict__ ws_i, int chunks, int64_t nq,
+                                                         int k, float* __restrict__ score, int64_t lds, int32_t* __restrict__ index, int64_t ldi) {
+  __shared__ float sm_s[4][TILE];
+  __shared__ int sm_i[4][TILE];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t r = (int64_t)blockIdx.x * 4 + wv;
+  if (r >= nq) return;
+  float ls = -__builtin_inff();
+  int li = -1, n = 0;
+  for (int c = 0; c < chunks; c++) {
+    const int64_t off = ((int64_t)c * nq + r) * k;
+    const float cs = lane < k ? ws_s[off + lane] : -__builtin_inff();
+    const int ci = lane < k ? ws_i[off + lane] : -1;
+    const int cn = __builtin_popcountll(__ballot(ci >= 0));          // the entries are a prefix of the k slots
+    if (cn == 0) continue;
+    int pos_l = lane, pos_c = lane;
+    for (int e = 0; e < cn; e++) pos_l += topk_before(__shfl(cs, e, WAVE), __shfl(ci, e, WAVE), ls, li) ? 1 : 0;
+    for (int e = 0; e < n; e++) pos_c += topk_before(__shfl(ls, e, WAVE), __shfl(li, e, WAVE), cs, ci) ? 1 : 0;
+    if (lane < n && pos_l < k) {
+      sm_s[wv][pos_l] = ls;
+      sm_i[wv][pos_l] = li;
+    }
+    if (lane < cn && pos_c < k) {
+      sm_s[wv][pos_c] = cs;
+      sm_i[wv][pos_c] = ci;
+    }
+    n = n + cn < k ? n + cn : k;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    ls = lane < n ? sm_s[wv][lane] : -__builtin_inff();
+    li = lane < n ? sm_i[wv][lane] : -1;
+    __builtin_amdgcn_wave_barrier();          // the next chunk's stores stay behind these loads
+  }
+  if (lane < k) {
+    score[r * lds + lane] = ls;
+    index[r * ldi + lane] = li;
+  }
+}
+
 // ---- sum_{i<j} exp(-t * d2_ij): grid (T, T) tiles, blocks below the diagonal write 0; fp64 per-tile partials
 __global__ __launch_bounds__(256) void pair_gauss_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int64_t d, float t,
                                                          double* __restrict__ partials) {
@@ -324,6 +479,7 @@ __global__ __launch_bounds__(64) void probe_loss_accum_kernel(const float* __res
 }
 
 constexpr int RANK_TILES_PER_CHUNK = 16;
+constexpr int TOPK_TILES_PER_CHUNK = 16;          // 1024 targets per workgroup: the rank kernel's grid
 constexpr int64_t PROBE_ROWS_PER_CHUNK = 128;
 
 }  // namespace
@@ -345,6 +501,38 @@ extern "C" int mca_cosine_rank_f32(const float* q, int64_t ldq, const int32_t* q
   const int64_t ntiles = (nt + TILE - 1) / TILE, chunks = (ntiles + RANK_TILES_PER_CHUNK - 1) / RANK_TILES_PER_CHUNK;
   hipLaunchKernelGGL(rank_count_kernel, dim3((unsigned)((nq + TILE - 1) / TILE), (unsigned)chunks), dim3(256), 0, as_stream(stream), q, ldq,
                      qidx, nq, t, ldt, nt, d, RANK_TILES_PER_CHUNK, s_true, rank);
+  return launch_status();
+}
+
+static int64_t topk_chunks(int64_t nt) {
+  const int64_t ntiles = (nt + TILE - 1) / TILE;
+  return (ntiles + TOPK_TILES_PER_CHUNK - 1) / TOPK_TILES_PER_CHUNK;
+}
+
+extern "C" int64_t mca_cosine_topk_workspace(int64_t nq, int64_t nt, int k) {
+  if (nq < 0 || nt < 0 || k < 1 || k > MCA_TOPK_MAX) return -1;
+  return topk_chunks(nt) * nq * k * (int64_t)(sizeof(float) + sizeof(int32_t));
+}
+
+extern "C" int mca_cosine_topk_f32(const float* q, int64_t ldq, const int32_t* qidx, int64_t nq, const float* t, int64_t ldt, int64_t nt,
+                                   int64_t d, const uint8_t* tvalid, const int32_t* exclude, int k, void* ws, int64_t ws_bytes, float* score,
+                                   int64_t lds, int32_t* index, int64_t ldi, mca_stream_t stream) {
+  if (!q || !score || !index || (nt > 0 && !t) || nq < 0 || nt < 0 || d < 1 || k < 1) return MCA_E_BADARG;
+  if (k > MCA_TOPK_MAX) return MCA_E_UNSUPPORTED;
+  if (ldq < d || ldt < d || lds < k || ldi < k) return MCA_E_BADARG;
+  const int64_t need = mca_cosine_topk_workspace(nq, nt, k), chunks = topk_chunks(nt);
+  if (ws_bytes < need || (need > 0 && !ws)) return MCA_E_BADARG;
+  if (reinterpret_cast<uintptr_t>(ws) % alignof(float)) return MCA_E_ALIGN;
+  if (nt > INT32_MAX || chunks > 65535) return MCA_E_UNSUPPORTED;          // indices are int32; chunks are grid.y
+  if (nq == 0) return MCA_OK;
+  float* ws_s = static_cast<float*>(ws);
+  int32_t* ws_i = reinterpret_cast<int32_t*>(ws_s + chunks * nq * k);
+  if (chunks > 0)
+    hipLaunchKernelGGL(topk_chunk_kernel, dim3((unsigned)((nq + TILE - 1) / TILE), (unsigned)chunks), dim3(256),
+                       (size_t)TILE * k * (sizeof(float) + sizeof(int32_t)), as_stream(stream), q, ldq, qidx, nq, t, ldt, nt, d, tvalid, exclude,
+                       k, TOPK_TILES_PER_CHUNK, ws_s, ws_i);
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, as_stream(stream), ws_s, ws_i, (int)chunks, nq, k, score,
+                     lds, index, ldi);
   return launch_status();
 }
 

@@ -245,6 +245,8 @@ SIGNATURES = {
     "mca_nonfinite_flag": (_I, [C.POINTER(FiniteArgs), _P, _I, _P]),
     "mca_rows_normalize_f32": (_I, [_P, _I64, _P, _I64, _I64, _I64, _P]),
     "mca_cosine_rank_f32": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "mca_cosine_topk_workspace": (_I64, [_I64, _I64, _I]),
+    "mca_cosine_topk_f32": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _I, _P, _I64, _P, _I64, _P, _I64, _P]),
     "mca_pair_gauss_workspace": (_I64, [_I64]),
     "mca_pair_gauss_sum_f32": (_I, [_P, _I64, _I64, _I64, _F, _P, _I64, _P, _P, _P]),
     "mca_probe_nt_f32": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I, _F, C.c_uint64, _I64, _P]),

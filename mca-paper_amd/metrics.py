@@ -164,6 +164,95 @@ def cosine_ranks(queries: torch.Tensor, targets: torch.Tensor, index: torch.Tens
     return ranks
 
 
+TOPK_MAX = 64          # include/mca_hip.h MCA_TOPK_MAX
+
+
+def _topk_arguments(queries, targets, k, query_index, target_mask, exclude):
+    """cosine_topk's argument checks, on shapes and host values only (they raise with or without a HIP device): the selected
+    query rows as a cpu int64 tensor or None, the target mask as cpu bool or None, the exclusions as cpu int64 or None."""
+    if queries.dim() != 2 or targets.dim() != 2:
+        raise ValueError(f"expected 2-D (rows, features) tensors, got {tuple(queries.shape)} and {tuple(targets.shape)}")
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= TOPK_MAX:
+        raise ValueError(f"k must be an integer in 1..{TOPK_MAX}, got {k!r}")
+    if queries.shape[1] != targets.shape[1]:
+        raise ValueError(f"queries have {queries.shape[1]} features, targets {targets.shape[1]}")
+    if queries.shape[1] < 1:
+        raise ValueError("the rows have no features")
+    idx = None
+    if query_index is not None:
+        idx = torch.as_tensor(query_index).detach().reshape(-1).to(device="cpu", dtype=torch.int64)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= queries.shape[0]):
+            raise IndexError(f"query_index selects a row outside the {queries.shape[0]} query rows")
+    n = queries.shape[0] if idx is None else idx.numel()
+    mask = None
+    if target_mask is not None:
+        mask = torch.as_tensor(target_mask).detach().reshape(-1).to("cpu")
+        if mask.numel() != targets.shape[0]:
+            raise ValueError(f"target_mask has {mask.numel()} entries for {targets.shape[0]} targets")
+        mask = mask != 0
+    ex = None
+    if exclude is not None:
+        ex = torch.as_tensor(exclude).detach().reshape(-1).to(device="cpu", dtype=torch.int64)
+        if ex.numel() != n:
+            raise ValueError(f"exclude has {ex.numel()} entries for {n} queries")
+        ex = ex.clamp(min=-1, max=2 ** 31 - 1)          # anything below 0 or past the last target excludes nothing
+    return idx, mask, ex
+
+
+def cosine_topk(queries: torch.Tensor, targets: torch.Tensor, k: int, query_index=None, target_mask=None, exclude=None, device=None):
+    """The k nearest targets of every query by cosine, on the HIP top-k kernel: (scores (n, k) float32, indices (n, k) int64)
+    on the HIP device (``_hip_device(device)``; cpu inputs are copied there), n = the rows ``query_index`` selects (all when
+    None).  Rows are normalised as in ``cosine_ranks`` and a score is the same fmaf chain, so it is bitwise the value the rank
+    kernel compares.  ``target_mask`` (true = the target may be returned) and ``exclude`` (per query one target index that may
+    not, -1 for none) narrow the candidates; a NaN score is never returned.  Order: the higher score first, equal scores by
+    the lower index.  Columns past the number of candidates hold index -1 and score -inf.  The (n, targets) matrix is never
+    formed.  ValueError for k outside 1..64, a feature mismatch, a mask or exclusion of the wrong length, or no usable HIP
+    device; IndexError for a query_index outside the query rows: all before anything is launched."""
+    idx, mask, ex = _topk_arguments(queries, targets, k, query_index, target_mask, exclude)
+    k = int(k)
+    h = _hip()
+    dev = _hip_device(device)
+    q, t = normalize_rows(_device_f32(queries, dev)), normalize_rows(_device_f32(targets, dev))
+    n = q.shape[0] if idx is None else idx.numel()
+    idx = None if idx is None else idx.to(device=dev, dtype=torch.int32)
+    mask = None if mask is None else mask.to(device=dev, dtype=torch.uint8)
+    ex = None if ex is None else ex.to(device=dev, dtype=torch.int32)
+    need = h.lib().mca_cosine_topk_workspace(n, t.shape[0], k)
+    ws = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
+    score = torch.empty(n, k, dtype=torch.float32, device=dev)
+    index = torch.empty(n, k, dtype=torch.int32, device=dev)
+    h.call("mca_cosine_topk_f32", q.data_ptr(), q.shape[1], h.ptr(idx), n, t.data_ptr(), t.shape[1], t.shape[0], t.shape[1], h.ptr(mask),
+           h.ptr(ex), k, ws.data_ptr(), ws.numel(), score.data_ptr(), k, index.data_ptr(), k, h.stream_ptr())
+    return score, index.long()
+
+
+def knn_predict(scores: torch.Tensor, indices: torch.Tensor, labels: torch.Tensor, weighted: bool = False) -> torch.Tensor:
+    """The kNN readout of ``cosine_topk``'s result: per query the mean of ``labels[indices]`` over the valid neighbours
+    (index >= 0), weighted by ``scores.clamp_min(0)`` when ``weighted``.  labels (n,) -> (queries,), labels (n, L) ->
+    (queries, L), float32.  NaN where a row has no valid neighbour, and where ``weighted`` and all its weights are 0.
+    Plain torch on the device of ``indices``."""
+    valid = indices >= 0
+    w = valid.to(torch.float32)
+    if weighted:
+        w = w * scores.to(torch.float32).clamp_min(0)          # padding: 0 * max(-inf, 0) = 0
+    lab = labels.to(device=indices.device, dtype=torch.float32)
+    flat = lab.reshape(lab.shape[0], -1)
+    picked = flat[indices.clamp_min(0).long()]                             # (queries, k, L); padding picks row 0 ...
+    picked = torch.where(valid[..., None], picked, torch.zeros_like(picked))          # ... and drops it
+    total = w.sum(1, keepdim=True)
+    out = (picked * w[..., None]).sum(1) / total
+    out = torch.where(total > 0, out, torch.full_like(out, float("nan")))
+    return out.reshape(-1) if lab.dim() == 1 else out
+
+
+def hits_at(indices: torch.Tensor, positives: torch.Tensor, m: int) -> torch.Tensor:
+    """hit[r] = ``positives[r]`` is among the first ``m`` returned indices of row r: presence in the top-m list.  With the
+    reference's rank (the number of targets scoring STRICTLY higher than the true one) this equals ``rank < m`` except on exact
+    score ties: a true target tied with m or more lower-indexed targets has rank < m but no place among the first m."""
+    pos = torch.as_tensor(positives, device=indices.device).reshape(-1, 1).to(indices.dtype)
+    return ((indices[:, :m] == pos) & (pos >= 0)).any(1)
+
+
 def compute_cosines(embedding: torch.Tensor, embeddings: torch.Tensor) -> torch.Tensor:
     """utils/metrics.py:73-76: cosine of one vector against every row, (rows,) fp32 on the current HIP device, without the
     reference's (rows, D) repeat: normalised rows times the normalised vector on the HIP probe layer kernel."""
