@@ -23,8 +23,7 @@
 // Workgroup ids are remapped (xcd_remap) so that workgroups sharing operands sit on one XCD / L2.
 #include "common.h"
 #include "gemm_plan.h"          // tile geometry, LDS sizes and the dispatch rules (plain host C++)
-
-#define BK 64
+#include "gemm_tile.h"          // the device code the kernels share: operand images, staging, fragments, k-steps, stores
 
 static int num_cus() {
   static int n = 0;
@@ -51,11 +50,6 @@ __device__ __forceinline__ void ps_tile_decode(int tile, int tiles_m, int tiles_
   const int rem = tile - g * per_group;
   tn = rem / gh; tm = g * P + rem % gh;
 }
-
-// LDS image of a [128 rows][64 bf16] tile (128-byte rows): 16-byte chunk c of row r lives at chunk
-// c ^ ((r >> 1) & 7): a 16-lane group of ds_read_b128 (16 distinct rows, same logical chunk) then covers
-// all 64 banks exactly once.
-__device__ __forceinline__ int nt_off(int r, int c) { return r * 64 + ((c ^ ((r >> 1) & 7)) << 3); }
 
 // Fused GEGLU backward (model.py:35-38 autograd) for 8 consecutive columns n..n+7 of row m of dg = dY·W2 (fp32 in v):
 // h = [a | gate] (bf16, row stride ldh, halves ip apart);  dh_a = dg*gelu(gate),  dh_gate = dg*a*gelu'(gate).
@@ -84,7 +78,7 @@ __device__ __forceinline__ void geglu_bwd_piece(const float (&v)[8], const u16* 
   *reinterpret_cast<bf16x8*>(dh + m * ldh + ip + n) = dgt;
 }
 
-// Epilogue through LDS (BK = 64 kernels: the 64 KiB of operand buffers hold exactly one 128x128 fp32 tile).  The
+// Epilogue through LDS (the kernels with k-steps of 64: the 64 KiB of operand buffers hold exactly one 128x128 fp32 tile).  The
 // accumulators are written lane = column / register = row, then every thread reads whole 16-byte pieces of rows,
 // adds bias / residual with 16-byte loads and stores 16 bytes: 4x (fp32) or 8x (bf16) fewer store instructions,
 // every global access a full 128-byte-line segment of a row.
@@ -159,15 +153,7 @@ __device__ __forceinline__ void nt_epilogue_lds(f32x16 (&acc)[2][2], float* __re
                                                 const float* __restrict__ bias, const float* __restrict__ residual,
                                                 int64_t ldres, int64_t res_period, int M, int N, int m0, int n0, int wm, int wn,
                                                 int l31, int lh, int tid) {
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int row = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        cs[row * 128 + wn * 64 + j * 32 + l31] = acc[i][j][r];
-      }
+  acc_to_lds_tile(acc, cs, wm, wn, l31, lh);
   __syncthreads();
   nt_epilogue_rows<OUT_BF16, RES, EPI, 128, 256>(cs, Cv, ldc, bias, residual, ldres, res_period, M, N, m0, n0, tid);
 }
@@ -175,63 +161,9 @@ __device__ __forceinline__ void nt_epilogue_lds(f32x16 (&acc)[2][2], float* __re
 // ---------------------------------------------------------------------------------------------------------
 // NT kernel with direct global->LDS staging (global_load_lds_dwordx4): no staging VGPRs, no ds_write pass.
 // The LDS destination of one wave-instruction is linear (wave base + lane*16 B), so the XOR swizzle is applied
-// to the per-lane SOURCE address and again on the fragment reads (cdna guide, rule 21).
+// to the per-lane SOURCE address and again on the fragment reads (cdna guide, rule 21; the image and its swizzle: gemm_tile.h,
+// where the fragment addresses and the k-step nt_compute_step live too).
 // ---------------------------------------------------------------------------------------------------------
-template <int BKT> __device__ __forceinline__ int gl_sw(int r) { return BKT == 64 ? ((r >> 1) & 7) : ((r >> 2) & 3); }
-template <int BKT> __device__ __forceinline__ int gl_off(int r, int c) { return r * BKT + ((c ^ gl_sw<BKT>(r)) << 3); }
-
-// One BK = 64 step of a wavefront's 64x64 sub-tile: 4 k16-steps of 2x2 MFMA 32x32x16.  The fragment reads are
-// inline asm with hand-counted lgkmcnt so that the reads of step ks+1 are in flight while the MFMAs of step ks
-// issue (hipcc otherwise re-uses one register set and waits lgkmcnt(0) in front of every group of 4 MFMAs).
-// Byte address of (row r, k16-step ks): P ^ (32*ks) with P = tile_base + r*128 + 16*(lh ^ swizzle(r)); the XOR
-// form holds because every base is a multiple of 128 bytes.
-struct NtFragAddr { unsigned a[2], b[2]; };
-__device__ __forceinline__ NtFragAddr nt_frag_addr(const u16* lds_base, int a_elem_off, int b_elem_off, int wm, int wn, int l31, int lh) {
-  NtFragAddr f;
-  const unsigned base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const u16*)lds_base;
-#pragma unroll
-  for (int i = 0; i < 2; i++) {
-    const int ra = wm * 64 + i * 32 + l31, rb = wn * 64 + i * 32 + l31;
-    f.a[i] = base + 2u * (unsigned)a_elem_off + (unsigned)(ra * 128) + 16u * (unsigned)(lh ^ ((ra >> 1) & 7));
-    f.b[i] = base + 2u * (unsigned)b_elem_off + (unsigned)(rb * 128) + 16u * (unsigned)(lh ^ ((rb >> 1) & 7));
-  }
-  return f;
-}
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-#define NT_DSREAD(dst, addr) asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr))
-template <bool SWAP = false>          // SWAP: C^T = B.A^T (lane = row of C, registers = 4 consecutive columns)
-__device__ __forceinline__ void nt_compute_step(const NtFragAddr& f, unsigned stage_byte_off, f32x16 (&acc)[2][2]) {
-  u32x4v fa[2][2], fb[2][2];          // [parity][i]
-  const unsigned a0 = f.a[0] + stage_byte_off, a1 = f.a[1] + stage_byte_off;
-  const unsigned b0 = f.b[0] + stage_byte_off, b1 = f.b[1] + stage_byte_off;
-#define NT_ISSUE(KS, PAR)                                                                            \
-  NT_DSREAD(fa[PAR][0], a0 ^ (32u * (KS))); NT_DSREAD(fb[PAR][0], b0 ^ (32u * (KS)));                \
-  NT_DSREAD(fa[PAR][1], a1 ^ (32u * (KS))); NT_DSREAD(fb[PAR][1], b1 ^ (32u * (KS)));
-#define NT_MFMA(PAR)                                                                                 \
-  _Pragma("unroll") for (int i = 0; i < 2; i++)                                                      \
-    _Pragma("unroll") for (int j = 0; j < 2; j++)                                                    \
-      acc[i][j] = SWAP ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&fb[PAR][j]), \
-                                                                 *reinterpret_cast<const bf16x8*>(&fa[PAR][i]), acc[i][j], 0, 0, 0) \
-                       : __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&fa[PAR][i]), \
-                                                                 *reinterpret_cast<const bf16x8*>(&fb[PAR][j]), acc[i][j], 0, 0, 0);
-  NT_ISSUE(0, 0)
-  NT_ISSUE(1, 1)
-  asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-  NT_MFMA(0)
-  __builtin_amdgcn_sched_barrier(0);
-  NT_ISSUE(2, 0)
-  asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-  NT_MFMA(1)
-  __builtin_amdgcn_sched_barrier(0);
-  NT_ISSUE(3, 1)
-  asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-  NT_MFMA(0)
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-  NT_MFMA(1)
-#undef NT_ISSUE
-#undef NT_MFMA
-}
-
 template <bool OUT_BF16, int RES, int BKT, int EPI>
 __global__ __launch_bounds__(256) void gemm_nt_glds_kernel(
     const u16* __restrict__ A, int64_t lda, const u16* __restrict__ B, int64_t ldb, void* __restrict__ Cv,
@@ -265,21 +197,12 @@ __global__ __launch_bounds__(256) void gemm_nt_glds_kernel(
   auto stage = [&](int k0, int buf) {
 #pragma unroll
     for (int i = 0; i < NI; i++) {
-      u16* da = As + buf * TILE + (i * 4 + wave) * 512;
-      u16* db = Bs + buf * TILE + (i * 4 + wave) * 512;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ga[i] + k0),
-                                       (__attribute__((address_space(3))) void*)da, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gb[i] + k0),
-                                       (__attribute__((address_space(3))) void*)db, 16, 0, 0);
+      lds_dma16(ga[i] + k0, As + buf * TILE + (i * 4 + wave) * 512);
+      lds_dma16(gb[i] + k0, Bs + buf * TILE + (i * 4 + wave) * 512);
     }
   };
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+  acc_clear(acc);
 
   const int nkt = K / BKT;
   const NtFragAddr frag = nt_frag_addr(lds, 0, 2 * TILE, wm, wn, l31, lh);
@@ -327,7 +250,7 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(
     int64_t res_period, int M, int N, int K, int tiles_n, int nwg, const float* __restrict__ ln_mean = nullptr,
     const float* __restrict__ ln_rstd = nullptr, const float* __restrict__ ln_gamma = nullptr) {
   extern __shared__ __attribute__((aligned(16))) u16 lds2[];
-  constexpr int STAGE = (BM2 + BN) * 64;          // elements per stage: A tile then B tile
+  constexpr int STAGE = nt256_image::STAGE;
   const int tile = xcd_remap(blockIdx.x, nwg);
   const int tm = tile / tiles_n, tn = tile % tiles_n;
   const int m0 = tm * BM2, n0 = tn * BN;
@@ -335,38 +258,10 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, lh = lane >> 5;
 
-  const u16* ga[4];
-  const u16* gb[2];
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int p = (i * 8 + wave) * 64 + lane, r = p >> 3, c = (p & 7) ^ gl_sw<64>(r);
-    int ra = m0 + r; if (ra > M - 1) ra = M - 1;
-    ga[i] = A + (int64_t)ra * lda + c * 8;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; i++) {
-    const int p = (i * 8 + wave) * 64 + lane, r = p >> 3, c = (p & 7) ^ gl_sw<64>(r);
-    int rb = n0 + r; if (rb > N - 1) rb = N - 1;
-    gb[i] = B + (int64_t)rb * ldb + c * 8;
-  }
-  auto stage = [&](int k0, int st) {
-    u16* base = lds2 + st * STAGE;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ga[i] + k0),
-                                       (__attribute__((address_space(3))) void*)(base + (i * 8 + wave) * 512), 16, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gb[i] + k0),
-                                       (__attribute__((address_space(3))) void*)(base + BM2 * 64 + (i * 8 + wave) * 512), 16, 0, 0);
-  };
+  nt256_image img{wave, lane};
+  img.set_tile(A, lda, B, ldb, M, m0, [&](int r) { int rb = n0 + r; if (rb > N - 1) rb = N - 1; return rb; });
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+  acc_clear(acc);
 
   const int nkt = K / 64;
   const NtFragAddr frag = nt_frag_addr(lds2, 0, BM2 * 64, wm, wn, l31, lh);
@@ -385,15 +280,15 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(
     int m = m0 + (tid & 255); if (m > M - 1) m = M - 1;
     ln_val = tid < 256 ? ln_mean[m] : ln_rstd[m];
   }
-  stage(0, 0);
-  if (nkt > 1) stage(64, 1);
+  img.stage(lds2, 0, 0);
+  if (nkt > 1) img.stage(lds2, 64, 1);
   if (EPI == 2) lnstat[tid] = ln_val;          // visible to every wave after the k-loop's barriers
   int st = 0;
 #define NT256_STEP(KT, WAITN)                                                                  \
   {                                                                                            \
     wait_vmcnt(WAITN);                                                                         \
     __builtin_amdgcn_s_barrier();                                                              \
-    if ((KT) + 2 < nkt) { int s2 = st + 2; if (s2 >= 3) s2 -= 3; stage(((KT) + 2) * 64, s2); } \
+    if ((KT) + 2 < nkt) { int s2 = st + 2; if (s2 >= 3) s2 -= 3; img.stage(lds2, ((KT) + 2) * 64, s2); } \
     nt_compute_step(frag, (unsigned)st * (unsigned)(STAGE * 2), acc);                          \
     st = st == 2 ? 0 : st + 1;                                                                 \
   }
@@ -421,15 +316,7 @@ __global__ __launch_bounds__(512) void gemm_nt_256_kernel(
   __syncthreads();
   // epilogue through LDS: 256x128 fp32 = 128 KiB
   float* cs = reinterpret_cast<float*>(lds2);
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int row = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        cs[row * 128 + wn * 64 + j * 32 + l31] = acc[i][j][r];
-      }
+  acc_to_lds_tile(acc, cs, wm, wn, l31, lh);
   __syncthreads();
   if (PF) {
     // fast epilogue: residual already in registers, whole 128-column tile valid, 16-byte stores
@@ -519,7 +406,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
     int64_t ldc, const float* __restrict__ bias, const float* __restrict__ residual, int64_t ldres,
     int M, int N, int K, int tiles_n, int nwg, int dbg) {
   extern __shared__ __attribute__((aligned(16))) u16 lds2[];
-  constexpr int STAGE = (BM2 + BN) * 64;          // elements per stage: A tile then B tile
+  constexpr int STAGE = nt256_image::STAGE;
   constexpr bool BWD = MODE == 3 || MODE == 5, FWD = MODE == 4 || MODE == 6, SAVED = MODE >= 5;
   constexpr int NST = MODE == 0 ? 8 : (FWD ? 12 : 16);         // global stores per wave and tile
   constexpr int NPRE = (MODE == 2 || BWD) ? 16 : 1;
@@ -529,41 +416,18 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
   const int l31 = lane & 31, lh = lane >> 5;
   const int nkt = K / 64;
   const NtFragAddr frag = nt_frag_addr(lds2, 0, BM2 * 64, wm, wn, l31, lh);
-  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const u16*)lds2;
+  const unsigned lds_base = lds_addr(lds2);
   const unsigned scratch = lds_base + 2u * (unsigned)(STAGE * 2) + (unsigned)wave * 8192u;   // stage slot 2 and the 16 KiB after it
 
-  const u16* ga[4];
-  const u16* gb[2];
+  nt256_image img{wave, lane};
   const int tiles_m = nwg / tiles_n;
   const int flat_order = (dbg >> 5) & 31;          // knob 0 = 32: row-major tile order; 32*P: P panels per group (A/B)
   auto tile_ptrs = [&](int tile) {
     int tm, tn;
     ps_tile_decode(tile, tiles_m, tiles_n, flat_order, tm, tn);
-    const int m0 = tm * BM2, n0 = tn * BN;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int p = (i * 8 + wave) * 64 + lane, r = p >> 3, c = (p & 7) ^ gl_sw<64>(r);
-      int ra = m0 + r; if (ra > M - 1) ra = M - 1;
-      ga[i] = A + (int64_t)ra * lda + c * 8;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-      const int p = (i * 8 + wave) * 64 + lane, r = p >> 3, c = (p & 7) ^ gl_sw<64>(r);
-      // N % 128 == 0 (MODE 4: N % 64 == 0): no clamp.  MODE 4: tile rows 0..63 = "a" rows, 64..127 = "gate" rows
-      const int rb = FWD ? (r < 64 ? tn * 64 + r : N + tn * 64 + (r - 64)) : n0 + r;
-      gb[i] = B + (int64_t)rb * ldb + c * 8;
-    }
-  };
-  auto stage = [&](int k0, int st) {
-    u16* base = lds2 + st * STAGE;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ga[i] + k0),
-                                       (__attribute__((address_space(3))) void*)(base + (i * 8 + wave) * 512), 16, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gb[i] + k0),
-                                       (__attribute__((address_space(3))) void*)(base + BM2 * 64 + (i * 8 + wave) * 512), 16, 0, 0);
+    const int n0 = tn * BN;
+    // N % 128 == 0 (MODE 4: N % 64 == 0): no clamp.  MODE 4: tile rows 0..63 = "a" rows, 64..127 = "gate" rows
+    img.set_tile(A, lda, B, ldb, M, tm * BM2, [&](int r) { return FWD ? (r < 64 ? tn * 64 + r : N + tn * 64 + (r - 64)) : n0 + r; });
   };
 
   int v = blockIdx.x;                              // virtual block id: blockIdx.x + it * gridDim.x (same XCD every time)
@@ -571,8 +435,8 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
   const bool tracing = (dbg & 8) && blockIdx.x == 0 && tid == 0;
   int ti = 0;
   tile_ptrs(xcd_remap(v, nwg));
-  stage(0, 0);
-  stage(64, 1);
+  img.stage(lds2, 0, 0);
+  img.stage(lds2, 64, 1);
   bool first = true;
   while (v < nwg) {
     const int tile = xcd_remap(v, nwg);
@@ -580,12 +444,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
     ps_tile_decode(tile, tiles_m, tiles_n, flat_order, tm, tn);
     const int m0 = tm * BM2, n0 = tn * BN;
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < 2; j++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+    acc_clear(acc);
     // ---------------- k-loop: three-stage ring, DMA two k-steps ahead (as gemm_nt_256_kernel) ----------------
     // this wave's 64x64 block (MODE 4: columns of h: "a" part for wn = 0, "gate" part for wn = 1)
     const int mw = m0 + wm * 64, nw = FWD ? (wn == 0 ? tn * 64 : N + tn * 64) : n0 + wn * 64;
@@ -634,7 +493,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
       PS_STAMP();
       __builtin_amdgcn_s_barrier();
       PS_STAMP();
-      if (kt + 2 < nkt) { int s2 = st + 2; if (s2 >= 3) s2 -= 3; stage((kt + 2) * 64, s2); }
+      if (kt + 2 < nkt) { int s2 = st + 2; if (s2 >= 3) s2 -= 3; img.stage(lds2, (kt + 2) * 64, s2); }
       if (NLD > 0 && kt == nkt - 3) preload();
       nt_compute_step<true>(frag, (unsigned)st * (unsigned)(STAGE * 2), acc);
       st = st == 2 ? 0 : st + 1;
@@ -654,8 +513,8 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
     const bool has_next = vn < nwg;
     if (has_next) {
       tile_ptrs(xcd_remap(vn, nwg));
-      stage(0, 0);
-      stage(64, 1);
+      img.stage(lds2, 0, 0);
+      img.stage(lds2, 64, 1);
     }
     if (NLD > 0) { if (has_next) ps_wait_vm<12>(); else ps_wait_vm<0>(); }          // the epilogue's loads have landed (requested 3 k-steps ago)
     PS_STAMP();
@@ -835,7 +694,7 @@ __global__ __launch_bounds__(512) void gemm_nt_persist256_kernel(
   const int l31 = lane & 31, lh = lane >> 5;
   const int nkt = K / 32;
   const int tiles_m = nwg / tiles_n;
-  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const u16*)lds2;
+  const unsigned lds_base = lds_addr(lds2);
   const unsigned scratch = lds_base + 3u * (unsigned)(P2_STAGE * 2) + (unsigned)wave * 8192u;          // slot 3 and the 32 KiB after it
 
   // fragment byte addresses inside a stage: row R (64-byte rows), k16-step ks: R*64 + ((lh ^ sw(R)) << 4) ^ (32*ks)
@@ -865,10 +724,8 @@ __global__ __launch_bounds__(512) void gemm_nt_persist256_kernel(
     u16* base = lds2 + st * P2_STAGE;
 #pragma unroll
     for (int i = 0; i < 2; i++) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ga[i] + k0),
-                                       (__attribute__((address_space(3))) void*)(base + (i * 8 + wave) * 512), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gb[i] + k0),
-                                       (__attribute__((address_space(3))) void*)(base + 256 * 32 + (i * 8 + wave) * 512), 16, 0, 0);
+      lds_dma16(ga[i] + k0, base + (i * 8 + wave) * 512);
+      lds_dma16(gb[i] + k0, base + 256 * 32 + (i * 8 + wave) * 512);
     }
   };
 
@@ -883,37 +740,29 @@ __global__ __launch_bounds__(512) void gemm_nt_persist256_kernel(
     ps_tile_decode(tile, tiles_m, tiles_n, 0, tm, tn);
     const int m0 = tm * 256, n0 = tn * 256;
     f32x16 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+    acc_clear(acc);
     // FIVE slots of 32 KiB (the fifth is the half of the epilogue scratch that a k-loop does not need): stage kt lives in slot
     // kt % 5, stages 0..2 were issued by the previous tile's epilogue (or the prologue), stage 3 goes out at the top of the tile and
-    // stage kt + 4 in the middle of step kt.  The step is software-pipelined as in tn_256x256_tile: the six fragment reads of a
-    // k16-step sit in the MFMA gaps of the k16-step before it, and the step's one barrier between its two MFMA groups.
+    // stage kt + 4 in the middle of step kt.  The step is the software-pipelined one of gemm_tile.h (T256_GROUP_READING), shared
+    // with tn_256x256_tile; the read, the MFMA and the wait ladder are this kernel's.
     // vmcnt, in issue order per wave: S0 S1 S2 [NST epilogue stores of the previous tile] S3 S4 ...: a stage has landed once only
     // the operations issued after its DMA are outstanding (host: nkt >= 6).
     u32x4v fa[2][2], fb[2][4];          // [k16-step][block]
-#define P2_SB __builtin_amdgcn_sched_barrier(0);
-#define P2_RA(KS, I, SO) NT_DSREAD(fa[KS][I], (fa_addr[I] + (SO)) ^ (32u * (KS))); P2_SB
-#define P2_RB(KS, J, SO) NT_DSREAD(fb[KS][J], (fb_addr[J] + (SO)) ^ (32u * (KS))); P2_SB
+#define P2_RA(KS, I, SO) NT_DSREAD(fa[KS][I], (fa_addr[I] + (SO)) ^ (32u * (KS))); T256_SB
+#define P2_RB(KS, J, SO) NT_DSREAD(fb[KS][J], (fb_addr[J] + (SO)) ^ (32u * (KS))); T256_SB
 #define P2_MM(KS, I, J) acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&fb[KS][J]), \
-                                                                            *reinterpret_cast<const bf16x8*>(&fa[KS][I]), acc[I][J], 0, 0, 0); P2_SB
-#define P2_GROUP_READING(KS, KN, SO, MID)                                                                                    \
-      P2_MM(KS, 0, 0) MID P2_RA(KN, 0, SO) P2_MM(KS, 0, 1) P2_RB(KN, 0, SO) P2_MM(KS, 0, 2) P2_RB(KN, 1, SO) P2_MM(KS, 0, 3)   \
-      P2_RB(KN, 2, SO) P2_MM(KS, 1, 0) P2_RB(KN, 3, SO) P2_MM(KS, 1, 1) P2_RA(KN, 1, SO) P2_MM(KS, 1, 2) P2_MM(KS, 1, 3)
+                                                                            *reinterpret_cast<const bf16x8*>(&fa[KS][I]), acc[I][J], 0, 0, 0); T256_SB
+#define P2_GROUP_READING(KS, KN, SO, MID) T256_GROUP_READING(P2_RA, P2_RB, P2_MM, KS, KN, SO, MID)
     if (first) ps_wait_vm<8>(); else ps_wait_vm<8 + NST>();          // S0 has landed
     __builtin_amdgcn_s_barrier();                                     // ... for everyone, and every wave has left the previous epilogue
     stage(96, 3);
-    P2_SB
-    P2_RA(0, 0, 0u) P2_RB(0, 0, 0u) P2_RB(0, 1, 0u) P2_RB(0, 2, 0u) P2_RB(0, 3, 0u) P2_RA(0, 1, 0u)
+    T256_SB
+    T256_FIRST_READS(P2_RA, P2_RB)
     int slot = 0, prev = 4;
     for (int kt = 0; kt + 1 < nkt; kt++) {
       const unsigned so = (unsigned)slot * (unsigned)(P2_STAGE * 2);
       const int nxt = slot == 4 ? 0 : slot + 1;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); P2_SB
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); T256_SB
       P2_GROUP_READING(0, 1, so, )
       // stage kt + 1 has landed once only what was issued after it is outstanding; past the barrier every wave has finished with
       // stage kt - 1, whose slot takes stage kt + 4
@@ -922,20 +771,19 @@ __global__ __launch_bounds__(512) void gemm_nt_persist256_kernel(
       else if (kt + 2 < nkt) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
-      P2_SB
+      T256_SB
       const unsigned son = (unsigned)nxt * (unsigned)(P2_STAGE * 2);
       const bool fetch = kt + 4 < nkt;
-      P2_GROUP_READING(1, 0, son, if (fetch) stage((kt + 4) * 32, prev); P2_SB)
+      P2_GROUP_READING(1, 0, son, if (fetch) stage((kt + 4) * 32, prev); T256_SB)
       prev = slot; slot = nxt;
     }
     {          // the last stage: nothing left to wait for or to fetch
       const unsigned so = (unsigned)slot * (unsigned)(P2_STAGE * 2);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); P2_SB
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); T256_SB
       P2_GROUP_READING(0, 1, so, )
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); P2_SB
-      P2_MM(1, 0, 0) P2_MM(1, 0, 1) P2_MM(1, 0, 2) P2_MM(1, 0, 3) P2_MM(1, 1, 0) P2_MM(1, 1, 1) P2_MM(1, 1, 2) P2_MM(1, 1, 3)
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); T256_SB
+      T256_GROUP(P2_MM, 1)
     }
-#undef P2_SB
 #undef P2_RA
 #undef P2_RB
 #undef P2_MM
@@ -1021,31 +869,9 @@ __global__ __launch_bounds__(512) void gemm_nt_persist256_kernel(
 
 // =====================================================================================================
 // weight gradient:  C[N,K] += A[R,N]^T · B[R,K]
-// LDS image of a [64 r][128 cols] tile (256-byte rows): 16-byte chunk c (0..15) of row r at chunk
-// c ^ (4*(r & 3)): the four rows of one transposed 4x16 read then sit in four different 64-byte bank
-// quarters (conflict-free ds_read_b64_tr_b16).
+// (the operand images and their swizzle, the zero block, the transposed fragment reads, the k-step of the 64-row kernels and the
+// store of a wave's block: gemm_tile.h)
 // =====================================================================================================
-__device__ __forceinline__ int tn_off(int r, int c) { return r * 128 + ((c ^ ((r & 3) << 2)) << 3); }
-
-__device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-
-// fragment fetch by the transposed LDS read, and one parity's MFMA group (fa / fb / acc of the enclosing k-loop): shared by
-// the 128 x 128 and 256 x 128 kernels, TR_READ by the 256 x 256 one as well
-#define TR_READ(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define TN_MFMA(PAR)                                                             \
-  {                                                                            \
-    bf16x8 af[2], bfr[2];                                                      \
-    _Pragma("unroll") for (int i = 0; i < 2; i++) {                            \
-      const uint4 ua = make_uint4(fa[PAR][i][0][0], fa[PAR][i][0][1], fa[PAR][i][1][0], fa[PAR][i][1][1]); \
-      const uint4 ub = make_uint4(fb[PAR][i][0][0], fb[PAR][i][0][1], fb[PAR][i][1][0], fb[PAR][i][1][1]); \
-      af[i] = *reinterpret_cast<const bf16x8*>(&ua);                           \
-      bfr[i] = *reinterpret_cast<const bf16x8*>(&ub);                          \
-    }                                                                          \
-    _Pragma("unroll") for (int i = 0; i < 2; i++)                              \
-      _Pragma("unroll") for (int j = 0; j < 2; j++)                            \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0); \
-  }
-
 // DET (all four weight-gradient kernels): the deterministic forms' epilogue.  C is then the caller's scratch with ldc = K and
 // every row split STORES its partial tile into slot split_id (C + split_id * N * ldc) instead of adding it into C atomically;
 // det_reduce_kernel (elementwise.hip) adds the slots in ascending order.  DET = false is the code it always was.
@@ -1063,112 +889,49 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const u16* __restrict__ A,
   if (r_begin >= r_end) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wn = wave >> 1, wk = wave & 1;
-  const int lh = lane >> 5;
 
   // direct global->LDS staging: the tile image is 64 rows x 16 chunks (1024 chunks) per operand, 4 wave-instructions
-  // per wave; LDS position p = (i*4 + wave)*64 + lane holds logical chunk (p & 15) ^ ((row & 3) << 2) of row p >> 4.
-  // Rows past the end of this split and column chunks past N / K are fetched from a 16-byte zero block.
-  int srow[4];
-  const u16* pa[4];
-  const u16* pb[4];
-  bool ca_ok[4], cb_ok[4];
-  const u16* zero = reinterpret_cast<const u16*>(g_zero16);
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int p = (i * 4 + wave) * 64 + lane, r = p >> 4, c = (p & 15) ^ ((r & 3) << 2);
-    srow[i] = r;
-    ca_ok[i] = n0 + c * 8 < N;
-    cb_ok[i] = k0 + c * 8 < K;
-    pa[i] = A + n0 + c * 8;
-    pb[i] = B + k0 + c * 8;
-  }
+  // per wave, A and B in turn
+  tn_operand_image<4, 16, 4> ia, ib;
+  ia.set(A, n0, N, wave, lane);
+  ib.set(B, k0, K, wave, lane);
   auto stage = [&](int r0, int buf) {
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      const int r = r0 + srow[i];
-      const bool rok = r < r_end;
-      const u16* sa = (rok && ca_ok[i]) ? pa[i] + (int64_t)r * lda : zero;
-      const u16* sb = (rok && cb_ok[i]) ? pb[i] + (int64_t)r * ldb : zero;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sa,
-                                       (__attribute__((address_space(3))) void*)(As + buf * BR * 128 + (i * 4 + wave) * 512), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sb,
-                                       (__attribute__((address_space(3))) void*)(Bs + buf * BR * 128 + (i * 4 + wave) * 512), 16, 0, 0);
+      ia.load(i, r0, r_end, lda, As + buf * BR * 128, wave);
+      ib.load(i, r0, r_end, ldb, Bs + buf * BR * 128, wave);
     }
   };
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+  acc_clear(acc);
 
-  // per-lane transposed-read coordinates: 16-lane group g = lane>>4 covers matrix rows 16*(g&1)..+15 of the
-  // 32-row operand block and k-half lh; lane 4q+p supplies LDS row q, columns 4p..4p+3 of the 4x16 block.
-  // The reads are issued as inline asm with hand-counted lgkmcnt: hipcc otherwise orders every
-  // ds_read_b64_tr_b16 behind the LDS-DMA of the NEXT stage (s_waitcnt vmcnt(0) at the top of each step), which
-  // serialises the DMA with the MFMAs.  Byte address of (ks, t, i): lane_base[i] + buf*16384 + ks*4096 + t*1024.
-  const int tq = (lane & 15) >> 2, tp = lane & 3, tg = (lane >> 4) & 1;
-  unsigned abase[2], bbase[2];
-  {
-    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) u16*)lds;
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-      const int ca = wn * 64 + i * 32 + 16 * tg + 4 * tp, cb = wk * 64 + i * 32 + 16 * tg + 4 * tp;
-      abase[i] = lds0 + 2u * (unsigned)((8 * lh + tq) * 128 + (((ca >> 3) ^ (tq << 2)) << 3) + (ca & 7));
-      bbase[i] = lds0 + 2u * (unsigned)((8 * lh + tq) * 128 + (((cb >> 3) ^ (tq << 2)) << 3) + (cb & 7)) + 2u * 2 * BR * 128;
-    }
-  }
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+  // fragment byte address of (ks, t, i): base[i] + buf*16384 + ks*4096 + t*1024
+  const unsigned lds0 = lds_addr(lds), ldsb = lds0 + 2u * 2 * BR * 128;
+  const unsigned abase[2] = {tn_frag_base<128>(lds0, wn * 64, lane), tn_frag_base<128>(lds0, wn * 64 + 32, lane)};
+  const unsigned bbase[2] = {tn_frag_base<128>(ldsb, wk * 64, lane), tn_frag_base<128>(ldsb, wk * 64 + 32, lane)};
   const int nsteps = (r_end - r_begin + BR - 1) / BR;
   stage(r_begin, 0);
   __syncthreads();
   for (int st = 0; st < nsteps; st++) {
     const int cur = st & 1;
     if (st + 1 < nsteps) stage(r_begin + (st + 1) * BR, cur ^ 1);
-    const unsigned a0 = abase[0] + cur * 16384u, a1 = abase[1] + cur * 16384u;
-    const unsigned b0 = bbase[0] + cur * 16384u, b1 = bbase[1] + cur * 16384u;
-    u32x2 fa[2][2][2], fb[2][2][2];          // [parity][i][t]
-#define TN_ISSUE(KS, PAR)                                                        \
-    TR_READ(fa[PAR][0][0], a0, (KS) * 4096); TR_READ(fa[PAR][0][1], a0, (KS) * 4096 + 1024); \
-    TR_READ(fa[PAR][1][0], a1, (KS) * 4096); TR_READ(fa[PAR][1][1], a1, (KS) * 4096 + 1024); \
-    TR_READ(fb[PAR][0][0], b0, (KS) * 4096); TR_READ(fb[PAR][0][1], b0, (KS) * 4096 + 1024); \
-    TR_READ(fb[PAR][1][0], b1, (KS) * 4096); TR_READ(fb[PAR][1][1], b1, (KS) * 4096 + 1024);
-    TN_ISSUE(0, 0)
-    TN_ISSUE(1, 1)
-    asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-    TN_MFMA(0)
-    __builtin_amdgcn_sched_barrier(0);
-    TN_ISSUE(2, 0)
-    asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-    TN_MFMA(1)
-    __builtin_amdgcn_sched_barrier(0);
-    TN_ISSUE(3, 1)
-    asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-    TN_MFMA(0)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-    TN_MFMA(1)
+    tn_compute_step<4096, 1024>(abase[0] + cur * 16384u, abase[1] + cur * 16384u, bbase[0] + cur * 16384u, bbase[1] + cur * 16384u, acc);
     __syncthreads();
   }
-#undef TN_ISSUE
-  // C[n][k]: row n in registers, column k on the lane -> 128-byte contiguous atomic segments per row
-  const int l31 = lane & 31;
+  if (DET) {
+    tn_store_tile<true, 2>(acc, C + (int64_t)blockIdx.y * N * ldc, ldc, N, K, n0 + wn * 64, k0 + wk * 64, lane);
+  } else if (!(dbg & 1)) {
+    tn_store_tile<false, 2>(acc, C, ldc, N, K, n0 + wn * 64, k0 + wk * 64, lane);
+  } else {          // dbg & 1 (knob 2, timing ablation): no atomics; the compare keeps the accumulators alive
 #pragma unroll
-  for (int j = 0; j < 2; j++) {
-    const int k = k0 + wk * 64 + j * 32 + l31;
-    if (k >= K) continue;
+    for (int j = 0; j < 2; j++) {
+      if (k0 + wk * 64 + j * 32 + (lane & 31) >= K) continue;
 #pragma unroll
-    for (int i = 0; i < 2; i++)
+      for (int i = 0; i < 2; i++)
 #pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int n = n0 + wn * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if constexpr (DET) {
-          if (n < N) C[((int64_t)blockIdx.y * N + n) * ldc + k] = acc[i][j][r];
-        } else {
-          if (n < N && !(dbg & 1)) atomicAdd(C + (int64_t)n * ldc + k, acc[i][j][r]);
-          if ((dbg & 1) && acc[i][j][r] == 123.456f) C[0] = 1.f;
-        }
-      }
+        for (int r = 0; r < 16; r++)
+          if (acc[i][j][r] == 123.456f) C[0] = 1.f;
+    }
   }
 }
 
@@ -1177,8 +940,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const u16* __restrict__ A,
 // [64 r][256 n] + [64 r][128 k] (144 KiB) filled by global_load_lds two steps ahead, one raw s_barrier per step with a
 // counted vmcnt (same pipeline as gemm_nt_256_kernel), transposed fragment reads in inline asm.
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int tn_off256(int r, int c) { return r * 256 + ((c ^ ((r & 3) << 2)) << 3); }
-
 template <bool DET>
 __global__ __launch_bounds__(512) void gemm_tn_256_kernel(const u16* __restrict__ A, int64_t lda,
                                                            const u16* __restrict__ B, int64_t ldb, float* __restrict__ C,
@@ -1199,60 +960,24 @@ __global__ __launch_bounds__(512) void gemm_tn_256_kernel(const u16* __restrict_
   if (r_begin >= r_end) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wn = wave >> 1, wk = wave & 1;
-  const int lh = lane >> 5;
-  const u16* zero = reinterpret_cast<const u16*>(g_zero16);
 
-  int arow[4], brow[2];
-  const u16* pa[4];
-  const u16* pb[2];
-  bool ca_ok[4], cb_ok[2];
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int p = (i * 8 + wave) * 64 + lane, r = p >> 5, c = (p & 31) ^ ((r & 3) << 2);
-    arow[i] = r; ca_ok[i] = n0 + c * 8 < N; pa[i] = A + n0 + c * 8;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; i++) {
-    const int p = (i * 8 + wave) * 64 + lane, r = p >> 4, c = (p & 15) ^ ((r & 3) << 2);
-    brow[i] = r; cb_ok[i] = k0 + c * 8 < K; pb[i] = B + k0 + c * 8;
-  }
+  tn_operand_image<4, 32, 8> ia;          // [64 r][256 n]
+  tn_operand_image<2, 16, 8> ib;          // [64 r][128 k]
+  ia.set(A, n0, N, wave, lane);
+  ib.set(B, k0, K, wave, lane);
   auto stage = [&](int r0, int st) {
     u16* base = ldst + st * STAGE;
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int r = r0 + arow[i];
-      const u16* src = (r < r_end && ca_ok[i]) ? pa[i] + (int64_t)r * lda : zero;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(base + (i * 8 + wave) * 512), 16, 0, 0);
-    }
+    for (int i = 0; i < 4; i++) ia.load(i, r0, r_end, lda, base, wave);
 #pragma unroll
-    for (int i = 0; i < 2; i++) {
-      const int r = r0 + brow[i];
-      const u16* src = (r < r_end && cb_ok[i]) ? pb[i] + (int64_t)r * ldb : zero;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(base + BR * 256 + (i * 8 + wave) * 512), 16, 0, 0);
-    }
+    for (int i = 0; i < 2; i++) ib.load(i, r0, r_end, ldb, base + BR * 256, wave);
   };
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+  acc_clear(acc);
 
-  const int tq = (lane & 15) >> 2, tp = lane & 3, tg = (lane >> 4) & 1;
-  unsigned abase[2], bbase[2];
-  {
-    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) u16*)ldst;
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-      const int ca = wn * 64 + i * 32 + 16 * tg + 4 * tp, cb = wk * 64 + i * 32 + 16 * tg + 4 * tp;
-      abase[i] = lds0 + 2u * (unsigned)((8 * lh + tq) * 256 + (((ca >> 3) ^ (tq << 2)) << 3) + (ca & 7));
-      bbase[i] = lds0 + 2u * (unsigned)(BR * 256) + 2u * (unsigned)((8 * lh + tq) * 128 + (((cb >> 3) ^ (tq << 2)) << 3) + (cb & 7));
-    }
-  }
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+  const unsigned lds0 = lds_addr(ldst), ldsb = lds0 + 2u * (unsigned)(BR * 256);
+  const unsigned abase[2] = {tn_frag_base<256>(lds0, wn * 64, lane), tn_frag_base<256>(lds0, wn * 64 + 32, lane)};
+  const unsigned bbase[2] = {tn_frag_base<128>(ldsb, wk * 64, lane), tn_frag_base<128>(ldsb, wk * 64 + 32, lane)};
   const int nsteps = (r_end - r_begin + BR - 1) / BR;
   stage(r_begin, 0);
   if (nsteps > 1) stage(r_begin + BR, 1);
@@ -1263,48 +988,11 @@ __global__ __launch_bounds__(512) void gemm_tn_256_kernel(const u16* __restrict_
     __builtin_amdgcn_s_barrier();
     if (sp + 2 < nsteps) { int s2 = st + 2; if (s2 >= 3) s2 -= 3; stage(r_begin + (sp + 2) * BR, s2); }
     const unsigned so = (unsigned)st * (unsigned)(STAGE * 2);
-    const unsigned a0 = abase[0] + so, a1 = abase[1] + so, b0 = bbase[0] + so, b1 = bbase[1] + so;
-    u32x2 fa[2][2][2], fb[2][2][2];          // [parity][i][t]
-#define TN_ISSUE(KS, PAR)                                                        \
-    TR_READ(fa[PAR][0][0], a0, (KS) * 8192); TR_READ(fa[PAR][0][1], a0, (KS) * 8192 + 2048); \
-    TR_READ(fa[PAR][1][0], a1, (KS) * 8192); TR_READ(fa[PAR][1][1], a1, (KS) * 8192 + 2048); \
-    TR_READ(fb[PAR][0][0], b0, (KS) * 4096); TR_READ(fb[PAR][0][1], b0, (KS) * 4096 + 1024); \
-    TR_READ(fb[PAR][1][0], b1, (KS) * 4096); TR_READ(fb[PAR][1][1], b1, (KS) * 4096 + 1024);
-    TN_ISSUE(0, 0)
-    TN_ISSUE(1, 1)
-    asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-    TN_MFMA(0)
-    __builtin_amdgcn_sched_barrier(0);
-    TN_ISSUE(2, 0)
-    asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-    TN_MFMA(1)
-    __builtin_amdgcn_sched_barrier(0);
-    TN_ISSUE(3, 1)
-    asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-    TN_MFMA(0)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-    TN_MFMA(1)
+    tn_compute_step<8192, 2048>(abase[0] + so, abase[1] + so, bbase[0] + so, bbase[1] + so, acc);
     st = st == 2 ? 0 : st + 1;
   }
-#undef TN_ISSUE
-#undef TN_MFMA
-  const int l31 = lane & 31;
-#pragma unroll
-  for (int j = 0; j < 2; j++) {
-    const int k = k0 + wk * 64 + j * 32 + l31;
-    if (k >= K) continue;
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int n = n0 + wn * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if constexpr (DET) {
-          if (n < N) C[((int64_t)split_id * N + n) * ldc + k] = acc[i][j][r];          // split_id: the LOGICAL split (after xcd_remap)
-        } else {
-          if (n < N) atomicAdd(C + (int64_t)n * ldc + k, acc[i][j][r]);
-        }
-      }
-  }
+  // split_id: the LOGICAL split (after xcd_remap)
+  tn_store_tile<DET, 2>(acc, DET ? C + (int64_t)split_id * N * ldc : C, ldc, N, K, n0 + wn * 64, k0 + wk * 64, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1322,7 +1010,6 @@ __device__ __forceinline__ void tn_256x256_tile(const u16* __restrict__ A, int64
   if (r_begin >= r_end) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wn = wave >> 1, wk = wave & 1;
-  const int lh = lane >> 5;
   const u16* zero = reinterpret_cast<const u16*>(g_zero16);
 
   // DMA: an operand image is 1024 chunks of 16 B = 16 wave-instructions, two per wave; position p -> row p >> 5, chunk
@@ -1352,6 +1039,8 @@ __device__ __forceinline__ void tn_256x256_tile(const u16* __restrict__ A, int64
 #pragma unroll
     for (int i = 0; i < 2; i++) {
       const bool in = whole || r_next + srow[i] < r_end;
+      // (the builtin spelled out, not lds_dma16: through the wrapper the compiler reordered this block of the k-loop - m0 writes,
+      //  selects, loads - and the grouped launch measured 2 % slower)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(in ? cur_a[i] : zero),
                                        (__attribute__((address_space(3))) void*)(base + (i * 8 + wave_u) * 512), 16, 0, 0);
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(in ? cur_b[i] : zero),
@@ -1360,6 +1049,8 @@ __device__ __forceinline__ void tn_256x256_tile(const u16* __restrict__ A, int64
     }
     r_next += BR2;
   };
+  // (its own loop, not acc_clear: with the call the grouped kernel's registers came out differently - the listing loses the s_nop in
+  //  front of the k-step's first MFMA - and the grouped launch measured 2 % slower, profiles/gemm_tile_isa.md)
   f32x16 acc[2][4];
 #pragma unroll
   for (int i = 0; i < 2; i++)
@@ -1368,58 +1059,39 @@ __device__ __forceinline__ void tn_256x256_tile(const u16* __restrict__ A, int64
 #pragma unroll
       for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
 
-  // transposed-read coordinates as in gemm_tn_256_kernel: lane supplies LDS row 8*lh + tq (+4 for read t = 1, +16 per
-  // k16-step), columns 16*tg + 4*tp .. +3 of its 32-column operand block
-  const int tq = (lane & 15) >> 2, tp = lane & 3, tg = (lane >> 4) & 1;
-  unsigned abase[2], bbase[4];
-  {
-    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) u16*)ldst;
+  // transposed reads (tn_frag_base): + 4 rows for read t = 1, + 16 rows per k16-step
+  const unsigned lds0 = lds_addr(ldst), ldsb = lds0 + 2u * (unsigned)(BR2 * 256);
+  const unsigned abase[2] = {tn_frag_base<256>(lds0, wn * 64, lane), tn_frag_base<256>(lds0, wn * 64 + 32, lane)};
+  unsigned bbase[4];
 #pragma unroll
-    for (int i = 0; i < 2; i++) {
-      const int ca = wn * 64 + i * 32 + 16 * tg + 4 * tp;
-      abase[i] = lds0 + 2u * (unsigned)((8 * lh + tq) * 256 + (((ca >> 3) ^ (tq << 2)) << 3) + (ca & 7));
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int cb = wk * 128 + j * 32 + 16 * tg + 4 * tp;
-      bbase[j] = lds0 + 2u * (unsigned)(BR2 * 256) + 2u * (unsigned)((8 * lh + tq) * 256 + (((cb >> 3) ^ (tq << 2)) << 3) + (cb & 7));
-    }
-  }
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  // FIVE stages of 32 rows (all 160 KiB of LDS), DMA four steps ahead.  The step is software-pipelined: the fragments of one
-  // k16-step are read in the gaps between the MFMAs of the k16-step before it (two reads per gap, none in a burst), and the step's
-  // one barrier sits between its two MFMA groups, followed by one MFMA before the next stage's DMA is issued.
+  for (int j = 0; j < 4; j++) bbase[j] = tn_frag_base<256>(ldsb, wk * 128 + j * 32, lane);
+  // FIVE stages of 32 rows (all 160 KiB of LDS), DMA four steps ahead.  The step is the software-pipelined one of gemm_tile.h
+  // (T256_GROUP_READING): a block's two transposed reads per MFMA gap, the step's one barrier between its two MFMA groups, and one
+  // MFMA before the next stage's DMA is issued.
   const int nsteps = (r_end - r_begin + BR2 - 1) / BR2;
   stage(0);
   if (nsteps > 1) stage(1);
   if (nsteps > 2) stage(2);
   if (nsteps > 3) stage(3);
-  u32x2 fa[2][2][2], fb[2][4][2];          // [k16-step][block][t]
-#define TN2_SB __builtin_amdgcn_sched_barrier(0);
-#define TN2_RA(KS, I, SO) TR_READ(fa[KS][I][0], abase[I] + (SO), (KS) * 8192); TR_READ(fa[KS][I][1], abase[I] + (SO), (KS) * 8192 + 2048); TN2_SB
-#define TN2_RB(KS, J, SO) TR_READ(fb[KS][J][0], bbase[J] + (SO), (KS) * 8192); TR_READ(fb[KS][J][1], bbase[J] + (SO), (KS) * 8192 + 2048); TN2_SB
+  u32x2v fa[2][2][2], fb[2][4][2];          // [k16-step][block][t]
+#define TN2_RA(KS, I, SO) TR_READ(fa[KS][I][0], abase[I] + (SO), (KS) * 8192); TR_READ(fa[KS][I][1], abase[I] + (SO), (KS) * 8192 + 2048); T256_SB
+#define TN2_RB(KS, J, SO) TR_READ(fb[KS][J][0], bbase[J] + (SO), (KS) * 8192); TR_READ(fb[KS][J][1], bbase[J] + (SO), (KS) * 8192 + 2048); T256_SB
 #define TN2_AF(KS, I) __builtin_bit_cast(bf16x8, make_uint4(fa[KS][I][0][0], fa[KS][I][0][1], fa[KS][I][1][0], fa[KS][I][1][1]))
 #define TN2_BF(KS, J) __builtin_bit_cast(bf16x8, make_uint4(fb[KS][J][0][0], fb[KS][J][0][1], fb[KS][J][1][0], fb[KS][J][1][1]))
-#define TN2_MM(KS, I, J) acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(TN2_AF(KS, I), TN2_BF(KS, J), acc[I][J], 0, 0, 0); TN2_SB
-  // the MFMAs of k16-step KS with the reads of k16-step KN (at stage offset SO) in their gaps; MID runs after the first MFMA
-#define TN2_GROUP_READING(KS, KN, SO, MID)                                                              \
-    TN2_MM(KS, 0, 0) MID TN2_RA(KN, 0, SO) TN2_MM(KS, 0, 1) TN2_RB(KN, 0, SO) TN2_MM(KS, 0, 2) TN2_RB(KN, 1, SO) \
-    TN2_MM(KS, 0, 3) TN2_RB(KN, 2, SO) TN2_MM(KS, 1, 0) TN2_RB(KN, 3, SO) TN2_MM(KS, 1, 1) TN2_RA(KN, 1, SO)    \
-    TN2_MM(KS, 1, 2) TN2_MM(KS, 1, 3)
-#define TN2_GROUP(KS)                                                                                   \
-    TN2_MM(KS, 0, 0) TN2_MM(KS, 0, 1) TN2_MM(KS, 0, 2) TN2_MM(KS, 0, 3) TN2_MM(KS, 1, 0) TN2_MM(KS, 1, 1) TN2_MM(KS, 1, 2) TN2_MM(KS, 1, 3)
+#define TN2_MM(KS, I, J) acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(TN2_AF(KS, I), TN2_BF(KS, J), acc[I][J], 0, 0, 0); T256_SB
+#define TN2_GROUP_READING(KS, KN, SO, MID) T256_GROUP_READING(TN2_RA, TN2_RB, TN2_MM, KS, KN, SO, MID)
   if (nsteps > 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
   else if (nsteps > 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
   else if (nsteps > 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  TN2_SB
-  TN2_RA(0, 0, 0u) TN2_RB(0, 0, 0u) TN2_RB(0, 1, 0u) TN2_RB(0, 2, 0u) TN2_RB(0, 3, 0u) TN2_RA(0, 1, 0u)
+  T256_SB
+  T256_FIRST_READS(TN2_RA, TN2_RB)
   int st = 0, prev = TN2_NSTAGE - 1;
   for (int sp = 0; sp + 1 < nsteps; sp++) {
     const unsigned so = (unsigned)st * (unsigned)(TN2_STAGE * 2);
     const int nxt = st == TN2_NSTAGE - 1 ? 0 : st + 1;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); TN2_SB
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); T256_SB
     TN2_GROUP_READING(0, 1, so, )
     // stage sp + 1 has landed once only the (4 loads each of the) two younger stages are outstanding; past the barrier every
     // wavefront has finished with stage sp - 1, whose buffer takes stage sp + 4
@@ -1427,46 +1099,26 @@ __device__ __forceinline__ void tn_256x256_tile(const u16* __restrict__ A, int64
     else if (sp + 2 < nsteps) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    TN2_SB
+    T256_SB
     const unsigned son = (unsigned)nxt * (unsigned)(TN2_STAGE * 2);
     const bool fetch = sp + 4 < nsteps;
-    TN2_GROUP_READING(1, 0, son, if (fetch) stage(prev); TN2_SB)
+    TN2_GROUP_READING(1, 0, son, if (fetch) stage(prev); T256_SB)
     prev = st; st = nxt;
   }
   {          // the last stage: nothing left to wait for or to fetch
     const unsigned so = (unsigned)st * (unsigned)(TN2_STAGE * 2);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); TN2_SB
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); T256_SB
     TN2_GROUP_READING(0, 1, so, )
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); TN2_SB
-    TN2_GROUP(1)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); T256_SB
+    T256_GROUP(TN2_MM, 1)
   }
-#undef TN2_SB
 #undef TN2_RA
 #undef TN2_RB
 #undef TN2_AF
 #undef TN2_BF
 #undef TN2_MM
 #undef TN2_GROUP_READING
-#undef TN2_GROUP
-#undef TR_READ
-  // C[n][k]: row n in registers, column k on the lane -> 128-byte contiguous atomic segments per row
-  const int l31 = lane & 31;
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const int k = k0 + wk * 128 + j * 32 + l31;
-    if (k >= K) continue;
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int n = n0 + wn * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if constexpr (DET) {
-          if (n < N) C[(int64_t)n * ldc + k] = acc[i][j][r];
-        } else {
-          if (n < N) atomicAdd(C + (int64_t)n * ldc + k, acc[i][j][r]);
-        }
-      }
-  }
+  tn_store_tile<DET, 4>(acc, C, ldc, N, K, n0 + wn * 64, k0 + wk * 128, lane);
 }
 
 template <bool DET>
