@@ -237,6 +237,26 @@ typedef struct { const void* mask; uint8_t* rowmask; int32_t elem_bytes, n, offs
 typedef struct { mca_mask_desc m[MCA_MAX_MODALITIES]; int32_t n_mod, batch, n_tokens, n_fusion; } mca_pack_masks_args;
 int mca_pack_masks(const mca_pack_masks_args* args, uint8_t* padding, int32_t* present, mca_stream_t stream);
 
+/* mca_pack_masks with a per-step MODALITY DROPOUT drawn on the device (the reference's dead BatchDropout, utils/dataset.py).
+ * For local sample s, global sample g = sample0 + s, descriptor i and t = *step (read on the device, so a captured step draws
+ * new masks at every replay once the counter moves: mca_counter_add):
+ *   u(g, i, t) = top 24 bits of fmix64(seed ^ fmix64(t ^ fmix64((g << 32) | i))) * 2^-24   (fmix64: the murmur3 finaliser; the
+ *                draw of the MLP probe's dropout, mca_probe_nt_f32 act 2, with row = g and unit = i);
+ *   want_i = u < p[i] in float32 (p = 0 never drops, p = 1 always);   raw_i = mask i has a valid token in sample s;
+ *   keep_one != 0, some raw_i, and want_i for every i with raw_i: the raw-present modality with the largest u is rescued
+ *                (ties: the lowest i); a sample without a raw-present modality stays empty.
+ * A modality with want_i that is not rescued is DROPPED: every padding byte of its range and every byte of its rowmask is 1,
+ * present bit i is 0 and dropped[s] bit i is 1 (set whether or not raw_i; dropped may be NULL).  Everything else, fusion columns
+ * included, is what mca_pack_masks writes; with every p[i] == 0 the outputs are mca_pack_masks' byte for byte.  The input masks
+ * are only read.  On top of mca_pack_masks' checks: MCA_E_BADARG for drop or step NULL or any of the MCA_MAX_MODALITIES p[i]
+ * NaN or outside [0, 1] (zero the entries past n_mod); MCA_E_ALIGN for a step pointer that is not 8-byte aligned.               */
+typedef struct { float p[MCA_MAX_MODALITIES]; uint64_t seed; int64_t sample0; int32_t keep_one, pad_; } mca_modality_drop_args;
+int mca_pack_masks_drop(const mca_pack_masks_args* args, const mca_modality_drop_args* drop, const int64_t* step,
+                        uint8_t* padding, int32_t* present, int32_t* dropped, mca_stream_t stream);
+/* *counter += inc by one thread of a kernel (never a memset / copy node of a captured step).  MCA_E_BADARG: counter NULL;
+ * MCA_E_ALIGN: not 8-byte aligned.                                                                                              */
+int mca_counter_add(int64_t* counter, int64_t inc, mca_stream_t stream);
+
 /* Finite check of encoder inputs / pooled outputs without a host sync (encoders.py:197-198,206-213: the reference raises
  * after `.sum()` syncs).  *flag |= bit if any of the n[i] floats at p[i], i < count, is Inf or NaN.  The caller zeroes the
  * flag word, reads it once per step and passes it to mca_adamw_step as skip_flag.                                       */

@@ -64,6 +64,24 @@ def training_config(filename: str, make_output_dir: bool = True) -> Config:
     return cfg
 
 
+def modality_dropout_settings(cfg: Dict[str, Any]):
+    """The per-step modality dropout a training YAML asks for (FusionEngine.set_modality_dropout), or None.  Keys, all read with
+    ``get`` as ``predrop`` is (default_train_config keeps the reference's keys only): ``batch_dropout: true`` switches it on,
+    ``batch_dropout_seed`` (default: ``seed``), ``batch_dropout_keep_one`` (default true).  The rates are
+    ``modality_config[name]["dropout"]``, the key ``predrop`` reads and the reference's dead ``BatchDropout``
+    (utils/dataset.py) would have read; an entry without it raises KeyError, as ``predrop`` does.
+    -> {"rates": {name: p}, "seed": int, "keep_one": bool}"""
+    if not cfg.get("batch_dropout", False):
+        return None
+    modality_config = cfg.get("modality_config", cfg.get("modality_configs", {})) or {}
+    missing = [k for k, c in modality_config.items() if "dropout" not in c]
+    if missing:
+        raise KeyError(f"batch_dropout: modality_config entries without a 'dropout' key: {missing}")
+    return {"rates": {k: float(c["dropout"]) for k, c in modality_config.items()},
+            "seed": int(cfg.get("batch_dropout_seed", cfg.get("seed", 42))),
+            "keep_one": bool(cfg.get("batch_dropout_keep_one", True))}
+
+
 def get_cfg_defaults_embedding_eval() -> Config:
     """The probe's defaults: utils/config.py:129-153 of the reference, same 19 keys and values."""
     return Config(

@@ -109,6 +109,17 @@ static inline bool mca_dyn_lds(int bytes) {
   return true;
 }
 
+// Counter-based uniform in [0, 1) with 24 bits (murmur3 finaliser over (seed, step, row, unit)): the probe's dropout mask
+// (evaluate.hip) and the per-step modality dropout (elementwise.hip, row = global sample, unit = modality) draw from it
+__device__ __forceinline__ uint64_t fmix64(uint64_t k) {
+  k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
+  return k;
+}
+__device__ __forceinline__ float hash_uniform24(uint64_t seed, int64_t step, int64_t row, int64_t unit) {
+  const uint64_t h = fmix64(seed ^ fmix64((uint64_t)step ^ fmix64(((uint64_t)row << 32) | (uint64_t)unit)));
+  return (float)(h >> 40) * 5.9604644775390625e-8f;          // 24 bits -> [0, 1)
+}
+
 static inline hipStream_t as_stream(mca_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int launch_status() { return hipGetLastError() == hipSuccess ? MCA_OK : MCA_E_LAUNCH; }
 

@@ -950,7 +950,8 @@ __global__ __launch_bounds__(256) void pack_masks_kernel(mca_pack_masks_args a, 
   }
 }
 
-extern "C" int mca_pack_masks(const mca_pack_masks_args* args, uint8_t* padding, int32_t* present, mca_stream_t stream) {
+// the argument checks of both mask-packing entry points
+static int pack_masks_check(const mca_pack_masks_args* args, uint8_t* padding, int32_t* present) {
   if (!args || !padding || !present) return MCA_E_BADARG;
   if (args->n_mod <= 0 || args->n_mod > MCA_MAX_MODALITIES || args->batch <= 0 || args->n_tokens <= 0 || args->n_fusion < 0) return MCA_E_BADARG;
   int64_t tot = args->n_fusion;
@@ -961,8 +962,90 @@ extern "C" int mca_pack_masks(const mca_pack_masks_args* args, uint8_t* padding,
     if ((int64_t)d.offset + d.n > args->n_tokens) return MCA_E_BADARG;
     tot += d.n;
   }
-  if (tot > args->n_tokens) return MCA_E_BADARG;
+  return tot > args->n_tokens ? MCA_E_BADARG : MCA_OK;
+}
+
+extern "C" int mca_pack_masks(const mca_pack_masks_args* args, uint8_t* padding, int32_t* present, mca_stream_t stream) {
+  const int rc = pack_masks_check(args, padding, present);
+  if (rc != MCA_OK) return rc;
   hipLaunchKernelGGL(pack_masks_kernel, dim3(args->batch), dim3(256), 0, as_stream(stream), *args, padding, present);
+  return launch_status();
+}
+
+// mca_pack_masks with a per-(sample, modality, step) modality dropout drawn here (see include/mca_hip.h).  Two passes over the
+// sample's mask bytes: the first finds the raw presence bits, thread 0 then decides the drops (keep_one needs every raw bit),
+// the second writes what pack_masks_kernel writes with the dropped modalities' ranges forced to padded.
+__device__ __forceinline__ bool mask_padded(const mca_mask_desc& d, int64_t idx) {
+  return d.elem_bytes == 8 ? reinterpret_cast<const int64_t*>(d.mask)[idx] != 0 : reinterpret_cast<const uint8_t*>(d.mask)[idx] != 0;
+}
+__global__ __launch_bounds__(256) void pack_masks_drop_kernel(mca_pack_masks_args a, mca_modality_drop_args dr, const int64_t* __restrict__ step,
+                                                              uint8_t* __restrict__ padding, int32_t* __restrict__ present,
+                                                              int32_t* __restrict__ dropped) {
+  __shared__ int any_valid[MCA_MAX_MODALITIES];
+  __shared__ int drop_bits;
+  const int s = blockIdx.x, tid = threadIdx.x;
+  if (tid < MCA_MAX_MODALITIES) any_valid[tid] = 0;
+  __syncthreads();
+  for (int i = 0; i < a.n_mod; i++) {
+    const mca_mask_desc d = a.m[i];
+    bool valid = false;
+    for (int j = tid; j < d.n; j += 256) valid |= !mask_padded(d, (int64_t)s * d.n + j);
+    if (__any(valid) && (tid & 63) == 0) any_valid[i] = 1;          // benign race: every writer stores 1
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int64_t t = *step, g = dr.sample0 + s;
+    int raw = 0, want = 0, best = -1;
+    float best_u = -1.f;
+    for (int i = 0; i < a.n_mod; i++) {
+      const float u = hash_uniform24(dr.seed, t, g, i);
+      if (u < dr.p[i]) want |= 1 << i;
+      if (any_valid[i]) {
+        raw |= 1 << i;
+        if (u > best_u) { best_u = u; best = i; }          // strict: a tie keeps the lowest i
+      }
+    }
+    if (dr.keep_one && raw && (want & raw) == raw) want &= ~(1 << best);          // every present modality would go: rescue the largest u
+    drop_bits = want;
+    present[s] = raw & ~want;
+    if (dropped) dropped[s] = want;
+  }
+  __syncthreads();
+  const int drop = drop_bits;
+  uint8_t* prow = padding + (int64_t)s * a.n_tokens;
+  for (int i = 0; i < a.n_mod; i++) {
+    const mca_mask_desc d = a.m[i];
+    const bool gone = (drop >> i) & 1;
+    for (int j = tid; j < d.n; j += 256) {
+      const int64_t idx = (int64_t)s * d.n + j;
+      const uint8_t pad = (gone || mask_padded(d, idx)) ? 1 : 0;
+      prow[d.offset + j] = pad;
+      if (d.rowmask) d.rowmask[idx] = pad;
+    }
+  }
+  for (int j = a.n_tokens - a.n_fusion + tid; j < a.n_tokens; j += 256) prow[j] = 0;
+}
+
+extern "C" int mca_pack_masks_drop(const mca_pack_masks_args* args, const mca_modality_drop_args* drop, const int64_t* step,
+                                   uint8_t* padding, int32_t* present, int32_t* dropped, mca_stream_t stream) {
+  const int rc = pack_masks_check(args, padding, present);
+  if (rc != MCA_OK) return rc;
+  if (!drop || !step) return MCA_E_BADARG;
+  for (int i = 0; i < MCA_MAX_MODALITIES; i++)
+    if (!(drop->p[i] >= 0.f && drop->p[i] <= 1.f)) return MCA_E_BADARG;          // (NaN fails both comparisons)
+  if ((uintptr_t)step % 8) return MCA_E_ALIGN;
+  hipLaunchKernelGGL(pack_masks_drop_kernel, dim3(args->batch), dim3(256), 0, as_stream(stream), *args, *drop, step, padding, present, dropped);
+  return launch_status();
+}
+
+// *counter += inc by one thread of a kernel: a captured step keeps it as a kernel node, ordered like its neighbours
+__global__ void counter_add_kernel(int64_t* __restrict__ counter, int64_t inc) {
+  if (threadIdx.x == 0) *counter += inc;
+}
+extern "C" int mca_counter_add(int64_t* counter, int64_t inc, mca_stream_t stream) {
+  if (!counter) return MCA_E_BADARG;
+  if ((uintptr_t)counter % 8) return MCA_E_ALIGN;
+  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(64), 0, as_stream(stream), counter, inc);
   return launch_status();
 }
 

@@ -339,15 +339,9 @@ __global__ __launch_bounds__(256) void pair_gauss_final_kernel(const double* __r
   }
 }
 
-// ---- probe: counter-based dropout mask (murmur3 finaliser over (seed, step, row in batch, unit))
-__device__ __forceinline__ uint64_t fmix64(uint64_t k) {
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
-  return k;
-}
+// ---- probe: counter-based dropout mask (hash_uniform24 of common.h over (seed, step, row in batch, unit))
 __device__ __forceinline__ bool dropout_keep(uint64_t seed, int64_t step, int64_t row, int64_t unit, float p) {
-  const uint64_t h = fmix64(seed ^ fmix64((uint64_t)step ^ fmix64(((uint64_t)row << 32) | (uint64_t)unit)));
-  const float u = (float)(h >> 40) * 5.9604644775390625e-8f;          // 24 bits -> [0, 1)
-  return u >= p;
+  return hash_uniform24(seed, step, row, unit) >= p;
 }
 
 // Y[m, n] = act(X[idx[m]] . W[n] + bias[n]); act: 0 none, 1 ReLU, 2 dropout then ReLU (nn.Sequential order of the MLP probe)

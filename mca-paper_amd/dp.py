@@ -117,6 +117,9 @@ class DataParallelMCA:
         self.reducer.cut = self.cut
         eng.gather_hook = self._gather if (self.world > 1 or self.always) else None
         eng.grad_bucket_hook = self.reducer.bucket_ready
+        # modality dropout (FusionEngine.set_modality_dropout): local sample s is global sample rank * b + s, so W ranks with one
+        # seed draw the masks of the one-process step on the concatenated batch
+        eng.dropout_rank = dist.get_rank(self.group)
 
     def set_cut(self, cut):
         """cut(fn): how a collective is issued (None = call it); graph.GraphedStep installs its segment cutter here"""

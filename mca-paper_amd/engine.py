@@ -134,6 +134,12 @@ class FusionEngine:
         # (the *_det entry points of include/mca_hip.h), so a step is the same bits every time.  Off by default.
         self._deterministic = bool(self.dbg["deterministic"])
         self._captured = weakref.WeakSet()                  # live graph.GraphedStep objects: they replay the mode they captured
+        # Per-step modality dropout (set_modality_dropout): the settings, the step counter (one int64 word on the device, read by
+        # mca_pack_masks_drop and advanced by mca_counter_add inside the step) and this process' data-parallel rank, which places
+        # its local samples in the global batch (dp.DataParallelMCA.install)
+        self._mdrop: Optional[dict] = None
+        self._mdrop_counter: Optional[torch.Tensor] = None
+        self.dropout_rank = 0
 
     # ------------------------------------------------------------------------------------------------
     # parameters -> one flat buffer (and one for gradients)
@@ -267,6 +273,44 @@ class FusionEngine:
             for ws in self._ws.values():
                 if isinstance(ws, dict) and "T" in ws:
                     self._alloc_det_scratch(ws)
+
+    @property
+    def modality_dropout(self) -> Optional[dict]:
+        """the active per-step modality dropout, {"rates": {name: p}, "seed", "keep_one"}, or None"""
+        s = self._mdrop
+        return None if s is None else dict(rates=dict(s["rates"]), seed=s["seed"], keep_one=s["keep_one"])
+
+    def modality_dropout_step(self) -> int:
+        """the device step counter of the modality dropout: the t of the next draw.  Synchronises (tests, resume)."""
+        return 0 if self._mdrop_counter is None else int(self._mdrop_counter.item())
+
+    def set_modality_dropout(self, rates, seed: int = 42, keep_one: bool = True, step: int = 0):
+        """Per-step modality dropout, drawn on the device inside the step (mca_pack_masks_drop, include/mca_hip.h): every training
+        forward with a loss drops modality `name` of a sample with probability rates[name] (names not given: 0), a fresh draw per
+        (global sample, modality, step); keep_one rescues one modality of a sample that would lose all it has.  Eval, no_loss and
+        model.eval() forwards never drop and do not advance the step.  rates None or all zero switches it off.  `step` sets the
+        device counter (a resumed run passes its optimizer step count).  A captured step holds the launches and their by-value
+        arguments, so nothing here can change while a GraphedStep of this engine is alive."""
+        names = list(self.model.modality_types)
+        rates = dict(rates or {})
+        for k in rates:
+            if k not in names:
+                raise KeyError(f"set_modality_dropout: unknown modality '{k}' (known: {names})")
+        p = {n: float(rates.get(n, 0.0)) for n in names}
+        for n, v in p.items():
+            if not 0.0 <= v <= 1.0:          # (NaN fails both comparisons)
+                raise ValueError(f"set_modality_dropout: rate of '{n}' is {v}, not in [0, 1]")
+        on = any(v > 0.0 for v in p.values())
+        if on and not self.can_forward_backward():
+            raise NotImplementedError("set_modality_dropout needs native encoders (a torch encoder writes its padding itself)")
+        if len(self._captured):
+            raise RuntimeError("set_modality_dropout: a GraphedStep of this engine is alive and would go on replaying the "
+                               "launches it captured; delete it first")
+        if on and self._mdrop_counter is None:
+            self._mdrop_counter = torch.zeros(1, dtype=torch.int64, device=self.device)          # allocated once: the capture holds its address
+        if self._mdrop_counter is not None:
+            self._mdrop_counter.fill_(int(step))
+        self._mdrop = dict(rates=p, seed=int(seed) & 0xFFFFFFFFFFFFFFFF, keep_one=bool(keep_one)) if on else None
 
     def set_attention_dtype(self, dtype: str):
         """'bf16' (default) or 'fp8' (BASELINE configs[4]): the fusion layers' forward attention computes Q K^T and P V on the
@@ -416,6 +460,7 @@ class FusionEngine:
         ws["padding"] = u8(b, N)
         ws["present"] = torch.zeros(b, dtype=torch.int32, device=dev)
         ws["present_native"] = torch.zeros(b, dtype=torch.int32, device=dev)
+        ws["dropped"] = torch.zeros(b, dtype=torch.int32, device=dev)          # the modality dropout's drop bits (set_modality_dropout)
         # backward
         ws["dxa"], ws["dxb"], ws["dx_b"] = f32(T, D), f32(T, D), bf(T, D)
         ws["dg"], ws["do"] = bf(T, Ip), bf(T, D)
@@ -589,9 +634,11 @@ class FusionEngine:
     # ------------------------------------------------------------------------------------------------
     # forward
     # ------------------------------------------------------------------------------------------------
-    def _encode(self, batch, ws, need_grad: bool):
+    def _encode(self, batch, ws, need_grad: bool, drop: bool = False):
         """encoders + packing (model.py:455-466): writes ws['x'][0] (b, N, D), ws['padding'] (b, N) and ws['present'] (b,)
-        int32 (bit i = modality i has a valid token in that sample); returns modality_sample_mask {name: (b,) bool}."""
+        int32 (bit i = modality i has a valid token in that sample); returns modality_sample_mask {name: (b,) bool}.
+        drop: draw this step's modality dropout while packing (set_modality_dropout) and advance its step counter; the (b, M)
+        drop matrix is left in ws['dropped_cur'] (None when nothing was drawn)."""
         m, D, N, b = self.model, self.D, self.N, ws["b"]
         x0 = ws["x"][0]
         ws["foreign"] = {}
@@ -622,6 +669,17 @@ class FusionEngine:
         foreign = len(native_idx) != len(m.modality_types)
         if native_idx:
             pk.n_mod, pk.batch, pk.n_tokens, pk.n_fusion = len(native_idx), b, N, (0 if foreign else self.F)
+        ws["dropped_cur"] = None
+        if drop:          # (every encoder is native: set_modality_dropout refuses anything else)
+            s, da = self._mdrop, hip.ModalityDropArgs()
+            for k, mi in enumerate(native_idx):
+                da.p[k] = s["rates"][m.modality_types[mi]]
+            da.seed, da.sample0, da.keep_one = s["seed"], self.dropout_rank * b, int(s["keep_one"])
+            call("mca_pack_masks_drop", C.byref(pk), C.byref(da), ptr(self._mdrop_counter), ptr(ws["padding"]), ptr(ws["present_native"]),
+                 ptr(ws["dropped"]), stream_ptr())
+            call("mca_counter_add", ptr(self._mdrop_counter), 1, stream_ptr())
+            ws["dropped_cur"] = ((ws["dropped"][:, None] >> self._mod_shifts) & 1).to(torch.bool)
+        elif native_idx:
             call("mca_pack_masks", C.byref(pk), ptr(ws["padding"]), ptr(ws["present_native"]), stream_ptr())
         present = ws["present"]
         if not foreign:
@@ -924,7 +982,8 @@ class FusionEngine:
         self.refresh_weights()
         ws = self.workspace(b)
         ws["gen"] += 1          # the saved activations of any earlier forward of this batch size are gone from here on
-        sample_mask = self._encode(batch, ws, need_grad)
+        # the modality dropout is a training augmentation: eval, no_loss and model.eval() forwards keep today's launches
+        sample_mask = self._encode(batch, ws, need_grad, drop=self._mdrop is not None and m.training and not no_loss)
         pooled = self.forward_trunk(ws).view(b, self.R, self.D)
         slots = m.output_slots()
         if self.check_finite:
@@ -959,6 +1018,8 @@ class FusionEngine:
             out["fcl_loss"], out["no-fcl_loss"] = both[0], both[1]
         out["loss"] = loss.reshape(())
         out["modality_sample_mask"] = sample_mask
+        if ws["dropped_cur"] is not None:
+            out["modality_dropped"] = ws["dropped_cur"]          # (b, M) bool, this step's draw
         if self.check_finite and self.check_finite != "deferred":
             self.assert_finite()
         return out

@@ -10,7 +10,8 @@ learning rate and Adam bias corrections, ``mca_adamw_hyper``), optional copies i
 What makes the step capturable: every kernel takes its stream as an argument and nothing in the library allocates or
 synchronises (include/mca_hip.h); the finite checks are a device flag (no ``.item()``); the optimizer reads lr / bias
 corrections from device memory; all workspaces are allocated by the warm-up steps and the loss outputs come from the graph's
-private pool.
+private pool; the per-step modality dropout (FusionEngine.set_modality_dropout) reads its step from a device counter that a kernel of
+the captured step advances, so every replay draws the masks of the next step with no host work.
 
 Data parallelism (``dp=DataParallelMCA``): the step is captured as a CHAIN of graph segments cut at the collectives, which stay
 ordinary eager torch.distributed calls between two replays — forward | all-gather of the pooled block | loss + pooling backward |
@@ -49,7 +50,9 @@ class GraphedStep:
         self.static = {k: {kk: (vv.clone() if torch.is_tensor(vv) else vv) for kk, vv in v.items()} for k, v in batch.items()}
         # the warm-up steps are real optimizer steps: weights, moments and the step count are put back afterwards, so that
         # constructing a GraphedStep does not train (the capture itself executes nothing)
+        # (the modality dropout's step counter with them: the warm-up steps draw masks and advance it like any training step)
         saved = (eng.flat.clone(), optimizer.exp_avg.clone(), optimizer.exp_avg_sq.clone(), optimizer.step_count)
+        saved_drop_step = None if eng._mdrop_counter is None else eng._mdrop_counter.clone()
         cur = torch.cuda.current_stream()
         side = torch.cuda.Stream(device=eng.device)
         side.wait_stream(cur)
@@ -69,6 +72,8 @@ class GraphedStep:
         self.loss = self.out["loss"]
         eng.flat.copy_(saved[0]); optimizer.exp_avg.copy_(saved[1]); optimizer.exp_avg_sq.copy_(saved[2])
         optimizer.step_count = saved[3]
+        if saved_drop_step is not None:
+            eng._mdrop_counter.copy_(saved_drop_step)
         eng.invalidate_weights()
         eng.finite_flag.zero_(); eng._flag_host.zero_(); eng._flag_event = None
 

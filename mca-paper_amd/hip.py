@@ -53,6 +53,11 @@ class PackMasksArgs(C.Structure):
                 ("n_fusion", C.c_int32)]
 
 
+class ModalityDropArgs(C.Structure):
+    _fields_ = [("p", C.c_float * MAX_MODALITIES), ("seed", C.c_uint64), ("sample0", C.c_int64), ("keep_one", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
 class AttnFwdArgs(C.Structure):
     _fields_ = [
         ("q", C.c_void_p), ("q_bstride", C.c_int64), ("q_ld", C.c_int64),
@@ -222,6 +227,8 @@ SIGNATURES = {
     "mca_patch_ln_fwd": (_I, [_P, _I64, _I64, _I, _I, _I, _I, _I, _P, _P, _F, _F, _P, _P, _I64, _I, _P, _P, _P, _P]),
     "mca_patch_nd_ln_fwd": (_I, [_P, _I64, _I64, _I64, _I64, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _P, _P, _I64, _I, _P, _P, _P, _P]),
     "mca_pack_masks": (_I, [_P, _P, _P, _P]),
+    "mca_pack_masks_drop": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "mca_counter_add": (_I, [_P, _I64, _P]),
     "mca_build_keyinfo": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "mca_attn_vmean": (_I, [_P, _I64, _I64, _P, _I, _I, _I, _P]),
     "mca_attn_vmean_if_needed": (_I, [_P, _I64, _I64, _P, _I, _I, _I, _P, _I, _P]),

@@ -10,7 +10,7 @@ logging goes to stdout / <output_dir>/log.jsonl instead of wandb.  `--synthetic 
 the configured shapes when the HF dataset named in the YAML is not on disk.
 
 Log records (train_accel_gpu.py:126-130,163-181): every step (`--log-every N`: every N-th; each record costs a host sync, as the
-reference's `.to("cpu")` calls do) total_loss, the loss terms without '|', param_norm, grad_norm, lr; per eval batch val_step_*;
+reference's `.to("cpu")` calls do) total_loss, the loss terms without '|', param_norm, grad_norm, lr (and batch_dropout_rate with `batch_dropout: true`); per eval batch val_step_*;
 per epoch val_epoch_*.  Under data parallelism rank 0 logs ITS values, as `accelerator.log` does, the eval set is dealt to the
 ranks as Accelerate's prepared loader deals it (data.shard_eval_batches) and the embedding metrics gather every rank's rows.
 """
@@ -175,6 +175,14 @@ def main():
         meta = P.checkpoint.load_state(config.restart, model, opt)           # train_accel_gpu.py:97-99
         if rank == 0 and meta.get("warnings"):
             print("\n".join(meta["warnings"]), flush=True)
+    # batch_dropout: the per-step modality dropout drawn on the device inside the step, on top of any
+    # predrop.  Its step counter starts at the optimizer's step count, so a resumed run continues the stream of draws; set before
+    # a GraphedStep is captured.  The eval loop (model.eval()) never drops.
+    drop_cfg = P.config.modality_dropout_settings(config)
+    if drop_cfg is not None:
+        model.engine.set_modality_dropout(drop_cfg["rates"], seed=drop_cfg["seed"], keep_one=drop_cfg["keep_one"], step=opt.step_count)
+        if rank == 0:
+            print(f"batch_dropout: {model.engine.modality_dropout}", flush=True)
     log = open(os.path.join(config.output_dir, "log.jsonl"), "a") if rank == 0 else None
     step = config.start_epoch * steps_per_epoch
     if config.restart and "scheduler_last_epoch" in meta:          # the restored scheduler position, as load_state gives the reference
@@ -229,12 +237,17 @@ def main():
                 names = [k for k in outputs["losses"] if "|" not in k]
                 dev_vals = [loss.detach(), get_grad_norm(model), get_param_norm(model),
                             gnorm if gnorm is not None else torch.zeros((), device=device)] + [outputs["losses"][k].detach() for k in names]
+                dropped = outputs.get("modality_dropped")          # (b, M) bool: this step's modality dropout draw (batch_dropout)
+                if dropped is not None:
+                    dev_vals.append(dropped.float().mean())
                 host = torch.stack([torch.as_tensor(v, device=device).float().reshape(()) for v in dev_vals]).cpu().tolist()
                 total_loss, gn_ref, pn, g_all = host[0], host[1], host[2], (host[3] if gnorm is not None else None)
                 coef = min(1.0, config.clip / (g_all + 1e-6)) if (config.clip and g_all is not None) else 1.0
                 rec = {"epoch": epoch, "step": step, "total_loss": total_loss, "lr": opt.param_groups[0]["lr"],
                        "param_norm": pn, "grad_norm": gn_ref * coef, "grad_norm_unclipped": g_all,
                        **dict(zip(names, host[4:]))}
+                if dropped is not None:
+                    rec["batch_dropout_rate"] = host[-1]          # the realised fraction of (sample, modality) pairs dropped
                 print(json.dumps(rec), flush=True)
                 log.write(json.dumps(rec) + "\n"); log.flush()
             if config.n_step_checkpoint and idb % config.n_step_checkpoint == 0 and rank == 0:
