@@ -504,6 +504,21 @@ int mca_contrastive_fwd_bwd(const float* pooled_all, const uint32_t* present_all
                             int B, int b_local, int row0, int R, int D,
                             float* term_loss, float* loss, float* d_pooled, float* d_logit_scale,
                             void* workspace, mca_stream_t stream);
+/* The same loss, outputs and meaning (model.py:175-233; utils/contrastive_loss_with_temperature.py:40-108,178-195) in a
+ * STREAMING form for gathered batches of thousands of rows (mca-paper_amd/cached.py): the Gram product and both gradient
+ * products run tile by tile on the fp32-input MFMA (exact fp32 products, fp32 accumulation) and the logits are recomputed in
+ * the gradient pass, so no (B, B) matrix is ever stored.  The workspace holds per-row statistics only (9 T B floats); no word
+ * of it is read before the same call has written it.  No atomics: every sum has a fixed order given by the shapes, two calls
+ * give the same bytes.  d_pooled (b_local, R, D) is written at every element, zeros in the slots no term names.
+ * Accepted: every B >= 1 with b_local | B, every T, R <= 65535 and 1 <= D <= 512.  MCA_E_UNSUPPORTED, nothing launched: D > 512
+ * (the caller uses mca_contrastive_fwd_bwd).  MCA_E_BADARG, nothing launched: the dense form's refusals, or workspace_bytes <
+ * mca_contrastive_stream_workspace_bytes(B, T, R, D).                                                                       */
+int64_t mca_contrastive_stream_workspace_bytes(int B, int T, int R, int D);
+int mca_contrastive_stream_fwd_bwd(const float* pooled_all, const uint32_t* present_all,
+                                   const mca_loss_term* terms, int T, const float* logit_scale,
+                                   int B, int b_local, int row0, int R, int D,
+                                   float* term_loss, float* loss, float* d_pooled, float* d_logit_scale,
+                                   void* workspace, int64_t workspace_bytes, mca_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * clip_grad_norm_ + AdamW over one flat buffer (train_accel_gpu.py:116-118; torch AdamW defaults)

@@ -71,6 +71,11 @@ int mca_dbg_plan_layernorm_bwd(const struct mca_ln_bwd_problem* problem, struct 
  * (T, B, 4) fp32 = {lse of row i, lse of column i, ce_row + ce_col, dsum}, w is (T, W) fp32 with room for W = B ranks.  The entry
  * point and mca_contrastive_workspace_bytes (= w offset + w bytes + 256) place the regions by this function.  Pure host code. */
 int mca_dbg_contrastive_layout(int B, int T, int64_t* out);
+/* The tile constants and the workspace of mca_contrastive_stream_fwd_bwd: out[14] = {TI owner rows of a block, TJ other-side rows
+ * of a tile step, TK columns of D staged per step, the largest D, then (byte offset, bytes) of lse (2, T, B) fp32 (direction 0:
+ * rows, 1: columns), erat (2, T, B) = sum p l / sum p, diag (T, B) = l[i][i], the three (T, W) reduction arrays n / s / ds, and w
+ * (T, W)}, each (T, W) array with room for W = B.  MCA_E_BADARG: out NULL or a non-positive size.  Pure host code. */
+int mca_dbg_contrastive_stream_layout(int B, int T, int64_t* out);
 #ifdef __cplusplus
 }
 #endif

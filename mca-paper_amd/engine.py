@@ -36,6 +36,9 @@ FWD_BQ, FWD_BK = 128, 64
 BWD_BQ = 64          # query rows per step of the dK/dV pass (its key-block size: debug_options()['dkv_keys'])
 
 
+FLAG_CACHE_MISMATCH = 8          # the engine's flag word (encoder_steps.FLAG_INDEX_RANGE lists bits 1, 2, 4): cached.CachedStep(verify=True)
+
+
 def _pad_to(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
@@ -634,11 +637,13 @@ class FusionEngine:
     # ------------------------------------------------------------------------------------------------
     # forward
     # ------------------------------------------------------------------------------------------------
-    def _encode(self, batch, ws, need_grad: bool, drop: bool = False):
+    def _encode(self, batch, ws, need_grad: bool, drop: bool = False, sample0: Optional[int] = None, advance: bool = True):
         """encoders + packing (model.py:455-466): writes ws['x'][0] (b, N, D), ws['padding'] (b, N) and ws['present'] (b,)
         int32 (bit i = modality i has a valid token in that sample); returns modality_sample_mask {name: (b,) bool}.
         drop: draw this step's modality dropout while packing (set_modality_dropout) and advance its step counter; the (b, M)
-        drop matrix is left in ws['dropped_cur'] (None when nothing was drawn)."""
+        drop matrix is left in ws['dropped_cur'] (None when nothing was drawn).  sample0: the global index of the batch's first
+        sample in the draw (default: this rank's rows of the data-parallel batch); advance False leaves the step counter alone (the
+        chunks of a gradient-cached step, cached.py, draw at one counter value)."""
         m, D, N, b = self.model, self.D, self.N, ws["b"]
         x0 = ws["x"][0]
         ws["foreign"] = {}
@@ -674,10 +679,11 @@ class FusionEngine:
             s, da = self._mdrop, hip.ModalityDropArgs()
             for k, mi in enumerate(native_idx):
                 da.p[k] = s["rates"][m.modality_types[mi]]
-            da.seed, da.sample0, da.keep_one = s["seed"], self.dropout_rank * b, int(s["keep_one"])
+            da.seed, da.sample0, da.keep_one = s["seed"], (self.dropout_rank * b if sample0 is None else int(sample0)), int(s["keep_one"])
             call("mca_pack_masks_drop", C.byref(pk), C.byref(da), ptr(self._mdrop_counter), ptr(ws["padding"]), ptr(ws["present_native"]),
                  ptr(ws["dropped"]), stream_ptr())
-            call("mca_counter_add", ptr(self._mdrop_counter), 1, stream_ptr())
+            if advance:
+                call("mca_counter_add", ptr(self._mdrop_counter), 1, stream_ptr())
             ws["dropped_cur"] = ((ws["dropped"][:, None] >> self._mod_shifts) & 1).to(torch.bool)
         elif native_idx:
             call("mca_pack_masks", C.byref(pk), ptr(ws["padding"]), ptr(ws["present_native"]), stream_ptr())
@@ -773,6 +779,77 @@ class FusionEngine:
              row0, R, D, ptr(out["term_loss"]), ptr(out["loss"]), ptr(out["d_pooled"]), ptr(out["d_logit"]),
              ptr(self._ws[key]), stream_ptr())
         return out
+
+    # ------------------------------------------------------------------------------------------------
+    # the pieces of a gradient-cached step (cached.py): nothing above calls them
+    # ------------------------------------------------------------------------------------------------
+    def loss_kernel_for(self, B: int, choice: str = "auto") -> str:
+        """"dense" or "stream" for a bank of B rows.  auto: the streaming kernel wherever the dense workspace would be more than eight
+        times the streaming one, about T B^2 against 9 T B floats: from B = 68 (14 terms) to 74 (one term) on.  That lies below the size from which
+        the streaming kernel measured faster (it ties the dense one at B = 256, profiles/cached_step.md), so the workspace rule alone
+        decides and no timing threshold is kept.  Dense where the streaming kernel refuses the width."""
+        if choice not in ("auto", "dense", "stream"):
+            raise ValueError(f"loss_kernel is '{choice}', not one of auto, dense, stream")
+        lay = hip.contrastive_stream_layout(B, self.n_terms)
+        if self.D > lay["DMAX"]:
+            if choice == "stream":
+                raise hip.MCAHipError(f"the streaming loss kernel takes D <= {lay['DMAX']}, the model has D = {self.D}")
+            return "dense"
+        if choice != "auto":
+            return choice
+        L = hip.lib()
+        big = L.mca_contrastive_workspace_bytes(B, self.n_terms) > 8 * L.mca_contrastive_stream_workspace_bytes(B, self.n_terms, self.R, self.D)
+        return "stream" if big else "dense"
+
+    def loss_fwd_bwd_bank(self, bank, present_all, kernel: str):
+        """The loss over a caller-owned (B, R, D) bank as ONE rank of B rows (b_local = B, row0 = 0) with the kernel named: "dense"
+        (mca_contrastive_fwd_bwd) or "stream" (mca_contrastive_stream_fwd_bwd).  -> loss_fwd_bwd's dict, d_pooled (B, R, D)."""
+        B, R, D, T = bank.shape[0], self.R, self.D, self.n_terms
+        if kernel == "dense":
+            return self.loss_fwd_bwd(bank, present_all, B, 0)
+        dev, L = self.device, hip.lib()
+        nbytes = L.mca_contrastive_stream_workspace_bytes(B, T, R, D)
+        key = ("lossws_stream", B)
+        if key not in self._ws:
+            self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = dict(term_loss=torch.empty(T, dtype=torch.float32, device=dev), loss=torch.empty(1, dtype=torch.float32, device=dev),
+                   d_pooled=torch.empty(B, R, D, dtype=torch.float32, device=dev),
+                   d_logit=torch.empty(1, dtype=torch.float32, device=dev))
+        ls = self.model.loss.loss_fn.logit_scale
+        call("mca_contrastive_stream_fwd_bwd", ptr(bank), ptr(present_all), ptr(self.loss_terms_dev), T, ptr(ls.data), B, B, 0, R, D,
+             ptr(out["term_loss"]), ptr(out["loss"]), ptr(out["d_pooled"]), ptr(out["d_logit"]), ptr(self._ws[key]), nbytes, stream_ptr())
+        return out
+
+    def forward_chunk(self, batch, sample0: int):
+        """Forward of one chunk to its pooled tokens, without the loss and repeatable: in training mode the modality dropout (if set)
+        is drawn for global samples sample0 .. sample0 + b - 1 at the current step counter, which is NOT advanced, so a second call
+        draws the same masks; the finite flags are OR-ed into the device word and nothing here clears it.  Native encoders only
+        (can_forward_backward()): their forward always leaves in the workspace what backward(ws, ...) needs, as forward_backward
+        relies on.  -> (ws, pooled (b, R, D) view of the workspace, modality_sample_mask)."""
+        m = self.model
+        b = next(iter(batch[m.modality_types[0]].values())).shape[0]
+        if self.check_finite:
+            self._flag_inputs(batch)
+        self.refresh_weights()
+        ws = self.workspace(b)
+        ws["gen"] += 1
+        sample_mask = self._encode(batch, ws, False, drop=self._mdrop is not None and m.training, sample0=sample0, advance=False)
+        pooled = self.forward_trunk(ws).view(b, self.R, self.D)
+        if self.check_finite:
+            self._flag_tensors([pooled], 2)
+        return ws, pooled, sample_mask
+
+    def advance_modality_dropout(self):
+        """the step counter of the modality dropout + 1, by a kernel: once per gradient-cached step, as a plain step does"""
+        if self._mdrop is not None and self.model.training:
+            call("mca_counter_add", ptr(self._mdrop_counter), 1, stream_ptr())
+
+    def publish_flags(self):
+        """the finite / index flag word to its pinned mirror, with the event poll_finite() and assert_finite() wait for"""
+        if self.check_finite:
+            call("mca_flag_to_host", ptr(self.finite_flag), self._flag_host.data_ptr(), stream_ptr())
+            self._flag_event = torch.cuda.Event()
+            self._flag_event.record()
 
     # ------------------------------------------------------------------------------------------------
     # backward
@@ -1049,6 +1126,9 @@ class FusionEngine:
         self.finite_flag.zero_()
         self._flag_host.zero_()
         self._flag_event = None
+        if bits & FLAG_CACHE_MISMATCH:
+            raise RuntimeError("gradient-cached step: a chunk's second forward did not reproduce the pooled tokens of its first "
+                               "(CachedStep(verify=True)); the step's update is skipped")
         if bits & FLAG_INDEX_RANGE:
             raise IndexError("a token index is outside its encoder's table (the lookup skipped it; the step's update is skipped)")
         if bits & 1:

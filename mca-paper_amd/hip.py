@@ -246,6 +246,8 @@ SIGNATURES = {
     "mca_attn_bwd_dkv_fp8": (_I, [C.POINTER(AttnBwd2Args), C.POINTER(AttnFp8BwdOperands), _P]),
     "mca_contrastive_workspace_bytes": (_I64, [_I, _I]),
     "mca_contrastive_fwd_bwd": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mca_contrastive_stream_workspace_bytes": (_I64, [_I, _I, _I, _I]),
+    "mca_contrastive_stream_fwd_bwd": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I64, _P]),
     "mca_grad_sqnorm": (_I, [_P, _I64, _P, _P]),
     "mca_adamw_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P]),
     "mca_adamw_hyper": (_I, [_P, _F, _F, _F, _P]),
@@ -289,6 +291,7 @@ DEBUG_SIGNATURES = {
     "mca_dbg_plan_layernorm_fwd": (_I, [C.POINTER(LnFwdProblem), C.POINTER(LnFwdPlan)]),
     "mca_dbg_plan_layernorm_bwd": (_I, [C.POINTER(LnBwdProblem), C.POINTER(LnBwdPlan)]),
     "mca_dbg_contrastive_layout": (_I, [_I, _I, C.POINTER(_I64)]),
+    "mca_dbg_contrastive_stream_layout": (_I, [_I, _I, C.POINTER(_I64)]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -376,6 +379,17 @@ def contrastive_layout(B: int, T: int) -> dict:
     out = (_I64 * 6)()
     check(lib().mca_dbg_contrastive_layout(B, T, out), "mca_dbg_contrastive_layout")
     return {"G": (out[0], out[1]), "stats": (out[2], out[3]), "w": (out[4], out[5])}
+
+
+def contrastive_stream_layout(B: int, T: int) -> dict:
+    """mca_contrastive_stream_fwd_bwd's tile constants TI, TJ, TK, DMAX and {region: (byte offset, bytes)} of its workspace for
+    region in lse, erat, diag, red, w (include/mca_hip_debug.h)"""
+    out = (_I64 * 14)()
+    check(lib().mca_dbg_contrastive_stream_layout(B, T, out), "mca_dbg_contrastive_stream_layout")
+    lay = {"TI": out[0], "TJ": out[1], "TK": out[2], "DMAX": out[3]}
+    for k, name in enumerate(("lse", "erat", "diag", "red", "w")):
+        lay[name] = (out[4 + 2 * k], out[5 + 2 * k])
+    return lay
 
 
 def check(rc: int, what: str):

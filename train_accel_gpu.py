@@ -7,7 +7,10 @@ Same YAML keys (utils/config.py), same loop order (forward, zero_grad, backward,
 schedule with warm-up, per-epoch checkpoint, final safetensors model).  What differs: the model step runs in the HIP
 kernels of mca-paper_amd, the optimizer is the fused clip+AdamW, data parallelism is mca-paper_amd/dp.py (RCCL), and
 logging goes to stdout / <output_dir>/log.jsonl instead of wandb.  `--synthetic STEPS` trains on synthetic batches of
-the configured shapes when the HF dataset named in the YAML is not on disk.
+the configured shapes when the HF dataset named in the YAML is not on disk.  The YAML key `grad_cache_chunks: n` (n > 1) makes every
+optimizer step a gradient-cached step over n loader batches (mca-paper_amd/cached.py): the contrastive
+batch is n x batch_size, an epoch has len(loader) // n steps (leftover batches are dropped), and the schedule and the checkpoint
+cadence count optimizer steps.  Not with --graph or more than one rank.
 
 Log records (train_accel_gpu.py:126-130,163-181): every step (`--log-every N`: every N-th; each record costs a host sync, as the
 reference's `.to("cpu")` calls do) total_loss, the loss terms without '|', param_norm, grad_norm, lr (and batch_dropout_rate with `batch_dropout: true`); per eval batch val_step_*;
@@ -28,6 +31,7 @@ sys.path.insert(0, REPO)
 P = importlib.import_module("mca-paper_amd")
 optim = importlib.import_module("mca-paper_amd.optim")
 dpmod = importlib.import_module("mca-paper_amd.dp")
+cached = importlib.import_module("mca-paper_amd.cached")
 from utils.training import get_grad_norm, get_param_norm  # noqa: E402  (the reference's import, train_accel_gpu.py:15)
 
 
@@ -63,6 +67,16 @@ def move_to(obj, device):
     if isinstance(obj, list):
         return [move_to(v, device) for v in obj]
     raise TypeError("Invalid type for move_to")
+
+
+def grouped(feed, n):
+    """lists of n consecutive batches of `feed`; what is left at the end is dropped"""
+    group = []
+    for batch in feed:
+        group.append(batch)
+        if len(group) == n:
+            yield group
+            group = []
 
 
 def run_eval(model, eval_batches, model_config, device, step_log=None, sync=False):
@@ -127,6 +141,8 @@ def main():
     torch.manual_seed(config.seed)
     model_config = P.config.get_model_config(config)
     modality_config = config.get("modality_config", config.get("modality_configs", {}))
+    n_cache = cached.grad_cache_chunks(config)
+    cached.refuse_with(n_cache, "--graph" in sys.argv, world)
 
     # ---- data
     if synthetic_steps:
@@ -134,7 +150,7 @@ def main():
             for i in range(synthetic_steps):
                 yield P.data.synthetic_batch(model_config, config.batch_size, seed=1234 + rank + 1000 * (epoch * synthetic_steps + i),
                                              p_drop=max([c.get("dropout", 0.0) for c in modality_config.values()] + [0.0]) if config.get("predrop") else 0.0)
-        steps_per_epoch = synthetic_steps
+        steps_per_epoch = synthetic_steps // n_cache
         eval_batches = None
     else:
         from torch.utils.data import DataLoader
@@ -153,7 +169,7 @@ def main():
             eval_dl = DataLoader(ds["test"], collate_fn=collate, batch_sampler=P.data.shard_eval_batches(len(ds["test"]), config.batch_size, world, rank))
         else:
             eval_dl = DataLoader(ds["test"], collate_fn=collate, batch_size=config.batch_size)
-        steps_per_epoch = len(train_dl)
+        steps_per_epoch = len(train_dl) // n_cache
 
         def batches(epoch):
             if sampler is not None:
@@ -196,6 +212,7 @@ def main():
         model.engine.set_deterministic(True)
         if rank == 0:
             print("deterministic mode: on (fixed-order parameter-gradient sums)", flush=True)
+    cstep = cached.CachedStep(model, opt, config.batch_size, clip=config.clip or 0.0) if n_cache > 1 else None
     lr_at = lambda st: config.lr * lr_factor(config.lr_scheduler_type, st * sched_stride, config.num_warmup_steps, total_steps * sched_stride)
     model.train()
     for epoch in range(config.start_epoch, config.epochs):
@@ -203,13 +220,22 @@ def main():
         # host -> device copies one batch ahead on a copy stream (data.DevicePrefetcher); MCA_PREFETCH=0: the reference's
         # synchronous move_to in the compute stream (train_accel_gpu.py:111)
         feed = batches(epoch)
+        if cstep is not None:
+            # grouped on the host, BEFORE the prefetcher: it hands out its own two buffer sets and refills one as soon as the consumer
+            # asks for the next item, so an item must be everything one optimizer step reads (a list of n batches is one item)
+            feed = grouped(feed, n_cache)
         if os.environ.get("MCA_PREFETCH", "1") != "0":
             feed = P.data.DevicePrefetcher(feed, device)
         for idb, batch in enumerate(feed):
             batch = move_to(batch, device)          # (no-op for batches the prefetcher already placed)
             for g in opt.param_groups:
                 g["lr"] = lr_at(step)
-            if use_graph:
+            if cstep is not None:          # `batch` is the list of this step's n loader batches
+                outputs = cstep.step(batch)
+                loss, gnorm = outputs["loss"], cstep.gnorm
+                step += 1
+                model.engine.poll_finite()
+            elif use_graph:
                 if graphed is None:
                     graphed = importlib.import_module("mca-paper_amd.graph").GraphedStep(model, opt, batch, clip=config.clip or 0.0, dp=dp)
                 loss = graphed.step(batch)
