@@ -75,6 +75,18 @@ int mca_gemm_nt_geglu_fwd_saved(const uint16_t* A, int64_t lda, const uint16_t* 
 int mca_gemm_nt_geglu_bwd_saved(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const uint16_t* s,
                                 uint16_t* dh, int64_t ldh, int64_t ip, int64_t M, int64_t K, mca_stream_t stream);
 
+/* Data-gradient GEMM + LayerNorm backward in one launch (model.py:24-31 autograd behind a Linear's): dy[M,N] = A[M,K]·B[N,K]^T
+ * (+ residual[M,N], may be NULL) is never stored; a workgroup owns whole rows of it and runs the row body of mca_layernorm_bwd's
+ * trunk form on them: dx (fp32) and dx_bf16 = rstd*(g - mean(g) - xhat*mean(g*xhat)) with g = dy*gamma, xhat = (x - mean)*rstd,
+ * and dgamma += sum_rows dy*xhat (fp32 atomics, one per column and workgroup).  dx, its bf16 copy and the statistics' use are
+ * bit for bit those of mca_gemm_nt (fp32, residual) followed by mca_layernorm_bwd; dgamma differs by the order of the atomic adds.
+ * dx may alias residual.  N == 512 and K >= 96 (MCA_E_UNSUPPORTED otherwise), K % 32 == 0, any M >= 1; lda/ldb/ld_bf16 % 8 == 0,
+ * ldres/ldx/lddx % 4 == 0, every base 16-byte aligned (MCA_E_ALIGN).                                                          */
+int mca_gemm_nt_res_lnbwd(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* residual, int64_t ldres,
+                          const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
+                          float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16, float* dgamma,
+                          int64_t M, int64_t N, int64_t K, mca_stream_t stream);
+
 /* C[N,K] += A[R,N]^T · B[R,K]   (weight gradient: reduction over the R token rows; fp32 atomics
  * into C, which the caller zeroes once per step).  lda/ldb % 8 == 0; N and K are arbitrary but the
  * rows of A / B must be readable up to the next multiple of 8 columns (lda >= roundup8(N) etc.).  */

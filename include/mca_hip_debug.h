@@ -39,7 +39,8 @@ int mca_debug_reset(void);
  * runtime.  Nothing is launched and no device is touched.  Return 0 or the MCA_E_* code the entry point would refuse the shape with.
  *   mca_dbg_plan_gemm_nt        entry 0 = mca_gemm_nt, 1 = _lnres, 2 = _geglu_fwd, 3 = _geglu_bwd (the last three read M, N = ip, K only;
  *                               kernel 0 from entry 2: the unfused pair mca_gemm_nt + mca_geglu_fwd),
- *                               4 = _geglu_fwd_saved, 5 = _geglu_bwd_saved (the plans of entries 2 and 3 with the saved kernel)
+ *                               4 = _geglu_fwd_saved, 5 = _geglu_bwd_saved (the plans of entries 2 and 3 with the saved kernel),
+ *                               6 = _res_lnbwd (reads M, N, K only: the full-row kernel, one workgroup per 128 rows)
  *   mca_dbg_plan_gemm_tn        mca_gemm_tn_acc (its rule does not read the CU count)
  *   mca_dbg_plan_gemm_tn_group  mca_gemm_tn_acc_group over n members of N[i] x K[i]: grouped or single launches, and the row partition
  *   mca_dbg_gemm_kernel_name    the template instantiation a plan's `kernel` value stands for */

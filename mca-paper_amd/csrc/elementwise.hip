@@ -3,6 +3,7 @@
 // row for the norms; 16-byte accesses wherever the layout allows.
 #include "common.h"
 #include "ln_plan.h"          // which LayerNorm kernel, which grid (plain host C++)
+#include "ln_rows.h"          // the trunk backward's row body, shared with the full-row GEMM epilogue (gemm.hip)
 #include "../../include/mca_hip_debug.h"
 
 // =====================================================================================================
@@ -349,36 +350,19 @@ __global__ __launch_bounds__(256) void ln_bwd_trunk_kernel(const float* __restri
       xb[i] = *reinterpret_cast<const float4*>(x + r1 * ldx + c); db[i] = *reinterpret_cast<const float4*>(dy + r1 * ldy + c);
     }
     const float ma = mean_in[r0], ra = rstd_in[r0], mb = mean_in[r1], rb = rstd_in[r1];
-    float s1a = 0.f, s2a = 0.f, s1b = 0.f, s2b = 0.f;
-    // xhat overwrites x, g = dy * gamma overwrites dy
-#define LNB_ELEM(X, D, G, DG, M, R, S1, S2, LIVE)  { const float xh_ = ((X) - (M)) * (R); const float g_ = (D) * (G); if (LIVE) (DG) += (D) * xh_; \
-                                                    (S1) += g_; (S2) += g_ * xh_; (X) = xh_; (D) = g_; }
-#pragma unroll
-    for (int i = 0; i < NI; i++) {
-      LNB_ELEM(xa[i].x, da[i].x, gm[i].x, dg[i].x, ma, ra, s1a, s2a, true)  LNB_ELEM(xa[i].y, da[i].y, gm[i].y, dg[i].y, ma, ra, s1a, s2a, true)
-      LNB_ELEM(xa[i].z, da[i].z, gm[i].z, dg[i].z, ma, ra, s1a, s2a, true)  LNB_ELEM(xa[i].w, da[i].w, gm[i].w, dg[i].w, ma, ra, s1a, s2a, true)
-      LNB_ELEM(xb[i].x, db[i].x, gm[i].x, dg[i].x, mb, rb, s1b, s2b, two)   LNB_ELEM(xb[i].y, db[i].y, gm[i].y, dg[i].y, mb, rb, s1b, s2b, two)
-      LNB_ELEM(xb[i].z, db[i].z, gm[i].z, dg[i].z, mb, rb, s1b, s2b, two)   LNB_ELEM(xb[i].w, db[i].w, gm[i].w, dg[i].w, mb, rb, s1b, s2b, two)
-    }
-#undef LNB_ELEM
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      s1a += __shfl_xor(s1a, o, WAVE); s2a += __shfl_xor(s2a, o, WAVE); s1b += __shfl_xor(s1b, o, WAVE); s2b += __shfl_xor(s2b, o, WAVE);
-    }
-    s1a *= inv_cols; s2a *= inv_cols; s1b *= inv_cols; s2b *= inv_cols;
+    // the row body (ln_rows.h, shared with the full-row GEMM epilogue): xhat overwrites x, g = dy * gamma overwrites dy
+    float s1a, s2a, s1b, s2b;
+    ln_bwd_rows_stats<NI>(xa, xb, da, db, gm, dg, ma, ra, mb, rb, two, inv_cols, s1a, s2a, s1b, s2b);
 #pragma unroll
     for (int i = 0; i < NI; i++) {
       const int c = (lane + 64 * i) * 4;
-      float4 o;
-      o.x = ra * (da[i].x - s1a - xa[i].x * s2a); o.y = ra * (da[i].y - s1a - xa[i].y * s2a);
-      o.z = ra * (da[i].z - s1a - xa[i].z * s2a); o.w = ra * (da[i].w - s1a - xa[i].w * s2a);
+      float4 o = ln_bwd_row_dx(da[i], xa[i], ra, s1a, s2a);
       if (dx) *reinterpret_cast<float4*>(dx + r0 * lddx + c) = o;
-      if (dx_bf16) { uint2 pk; pk.x = pack2bf(o.x, o.y); pk.y = pack2bf(o.z, o.w); *reinterpret_cast<uint2*>(dx_bf16 + r0 * ld_bf16 + c) = pk; }
+      if (dx_bf16) *reinterpret_cast<uint2*>(dx_bf16 + r0 * ld_bf16 + c) = ln_pack4bf(o);
       if (two) {
-        o.x = rb * (db[i].x - s1b - xb[i].x * s2b); o.y = rb * (db[i].y - s1b - xb[i].y * s2b);
-        o.z = rb * (db[i].z - s1b - xb[i].z * s2b); o.w = rb * (db[i].w - s1b - xb[i].w * s2b);
+        o = ln_bwd_row_dx(db[i], xb[i], rb, s1b, s2b);
         if (dx) *reinterpret_cast<float4*>(dx + r1 * lddx + c) = o;
-        if (dx_bf16) { uint2 pk; pk.x = pack2bf(o.x, o.y); pk.y = pack2bf(o.z, o.w); *reinterpret_cast<uint2*>(dx_bf16 + r1 * ld_bf16 + c) = pk; }
+        if (dx_bf16) *reinterpret_cast<uint2*>(dx_bf16 + r1 * ld_bf16 + c) = ln_pack4bf(o);
       }
     }
   }

@@ -7,6 +7,8 @@
 //                                                     recomputed; FF1 + GEGLU; W2 data gradient + GEGLU')
 //   mca_gemm_nt_geglu_fwd_saved / _bwd_saved          the two GEGLU fusions with the backward's factors [gelu(gate) | a gelu'(gate)]
 //                                                     kept in h's place: the backward epilogue only multiplies
+//   mca_gemm_nt_res_lnbwd                             the same GEMM (N = 512) owning whole rows of C, the trunk LayerNorm backward of
+//                                                     dy = C (+ residual) in its epilogue: dy is never stored
 //   mca_gemm_tn_acc C[N,K] += A[R,N]^T · B[R,K]      both operands reduction-major (weight gradient:
 //                                                     dW = dY^T · X), operands fetched from LDS with the
 //                                                     gfx950 transposed read ds_read_b64_tr_b16
@@ -19,11 +21,13 @@
 //   gemm_nt_256_kernel       256x128x64, three stages, one tile per workgroup; fp32 + residual outputs (residual tile
 //                            prefetched into registers; optional LayerNorm recompute), fallback for odd shapes
 //   gemm_nt_glds_kernel      128x128x64, two stages: small M
+//   gemm_nt_rows_kernel      128x512x32, three stages, one tile of whole rows per workgroup; LayerNorm-backward epilogue
 //   gemm_tn_256x256_kernel / gemm_tn_256_kernel / gemm_tn_kernel   weight gradient, split over rows + fp32 atomics
 // Workgroup ids are remapped (xcd_remap) so that workgroups sharing operands sit on one XCD / L2.
 #include "common.h"
 #include "gemm_plan.h"          // tile geometry, LDS sizes and the dispatch rules (plain host C++)
 #include "gemm_tile.h"          // the device code the kernels share: operand images, staging, fragments, k-steps, stores
+#include "ln_rows.h"            // the trunk LayerNorm backward's row body (the full-row kernel's epilogue)
 
 static int num_cus() {
   static int n = 0;
@@ -865,6 +869,196 @@ __global__ __launch_bounds__(512) void gemm_nt_persist256_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// FULL-ROW NT kernel (N = 512 exactly): one workgroup computes 128 WHOLE rows of C = A.B^T, so the LayerNorm that consumes C
+// runs on the tile before it leaves the CU and C itself is never written.  8 wavefronts as 2 (m) x 4 (n), each 64 x 128 = 2 x 4
+// accumulators (the per-wavefront shape of gemm_nt_persist256_kernel, operands NOT swapped: lane = column, register = row, k16-steps
+// ascending, i.e. the fp32 chain of gemm_nt_glds_kernel / gemm_nt_256_kernel).  k-steps of 32 through a ring of three 40 KiB stages
+// (A image [128][32], B image [512][32], the gl_sw<32> swizzle; 1 + 4 loads per wave and stage), DMA two to three steps ahead, one
+// barrier per step behind a counted vmcnt; the step is the software-pipelined one of gemm_tile.h (T256_GROUP_READING).
+// vmcnt per wave, in issue order: S0 S1 S2 | S3 (middle of step 0) | S4 ...: stage kt + 1 has landed once at most the 5 loads of
+// stage kt + 2 are outstanding (host: K >= 96, three steps).  The last step leaves nothing in flight: the epilogue is plain C++.
+// Epilogue, four passes of 32 rows through 64.5 KiB of the ring: pass p takes rows 16 (p & 1) .. + 15 of row block p >> 1 of both
+// wave rows (registers 8 (p & 1) .. + 7 of acc[p >> 1][.]), so every wave writes in every pass; then wave w owns rows 4 w .. 4 w + 3
+// of the pass, two at a time in the lane layout of the trunk LayerNorm kernels (element (lane + 64 i) * 4, NI = 2).
+// The epilogue (mca_gemm_nt_res_lnbwd): dy = A.B^T (+ residual) stays on chip; the row body of ln_bwd_trunk_kernel (ln_rows.h) makes dx
+// (fp32), its bf16 copy and the lane's dgamma partials; block reduction, then one atomic per column and workgroup.  dx may be the
+// residual: a row is read and written by one wavefront, the reads first.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(512) void gemm_nt_rows_kernel(
+    const u16* __restrict__ A, int64_t lda, const u16* __restrict__ B, int64_t ldb, const float* residual, int64_t ldres,
+    const float* __restrict__ x, int64_t ldx, const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+    const float* __restrict__ gamma, float* dx, int64_t lddx, u16* __restrict__ dx_bf16, int64_t ld_bf16, float* __restrict__ dgamma,
+    int M, int K, int nwg) {
+  extern __shared__ __attribute__((aligned(16))) u16 lds2[];
+  constexpr unsigned STAGE_BYTES = ROWS_STAGE * 2;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 2, wn = wave & 3;
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int nkt = K / ROWS_BK;
+  const int m0 = xcd_remap(blockIdx.x, nwg) * ROWS_BM;
+  const unsigned lds_base = lds_addr(lds2);
+
+  // fragment byte addresses inside a stage, as in gemm_nt_persist256_kernel: row R (64-byte rows), k16-step ks
+  unsigned fa_addr[2], fb_addr[4];
+#pragma unroll
+  for (int i = 0; i < 2; i++) { const int r = wm * 64 + i * 32 + l31; fa_addr[i] = lds_base + (unsigned)(r * 64 + ((lh ^ gl_sw<32>(r)) << 4)); }
+#pragma unroll
+  for (int j = 0; j < 4; j++) { const int r = wn * 128 + j * 32 + l31; fb_addr[j] = lds_base + (unsigned)(ROWS_BM * 64) + (unsigned)(r * 64 + ((lh ^ gl_sw<32>(r)) << 4)); }
+
+  const u16* ga;
+  const u16* gb[4];
+  {
+    const int p = wave * 64 + lane, r = p >> 2, c = (p & 3) ^ gl_sw<32>(r);
+    int ra = m0 + r; if (ra > M - 1) ra = M - 1;          // rows past M: clamped (loaded and computed, never stored)
+    ga = A + (int64_t)ra * lda + c * 8;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int p = (i * 8 + wave) * 64 + lane, r = p >> 2, c = (p & 3) ^ gl_sw<32>(r);          // r < 512 = N: no clamp
+    gb[i] = B + (int64_t)r * ldb + c * 8;
+  }
+  auto stage = [&](int k0, int st) {
+    u16* base = lds2 + st * ROWS_STAGE;
+    lds_dma16(ga + k0, base + wave * 512);
+#pragma unroll
+    for (int i = 0; i < 4; i++) lds_dma16(gb[i] + k0, base + ROWS_BM * ROWS_BK + (i * 8 + wave) * 512);
+  };
+
+  f32x16 acc[2][4];
+  acc_clear(acc);
+  stage(0, 0); stage(ROWS_BK, 1); stage(2 * ROWS_BK, 2);
+  u32x4v fa[2][2], fb[2][4];          // [k16-step][block]
+#define RW_RA(KS, I, SO) NT_DSREAD(fa[KS][I], (fa_addr[I] + (SO)) ^ (32u * (KS))); T256_SB
+#define RW_RB(KS, J, SO) NT_DSREAD(fb[KS][J], (fb_addr[J] + (SO)) ^ (32u * (KS))); T256_SB
+#define RW_MM(KS, I, J) acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&fa[KS][I]), \
+                                                                            *reinterpret_cast<const bf16x8*>(&fb[KS][J]), acc[I][J], 0, 0, 0); T256_SB
+#define RW_GROUP_READING(KS, KN, SO, MID) T256_GROUP_READING(RW_RA, RW_RB, RW_MM, KS, KN, SO, MID)
+  ps_wait_vm<10>();                                  // S0 has landed
+  __builtin_amdgcn_s_barrier();                      // ... for everyone
+  T256_SB
+  T256_FIRST_READS(RW_RA, RW_RB)
+  int slot = 0;
+  for (int kt = 0; kt + 1 < nkt; kt++) {
+    const unsigned so = (unsigned)slot * STAGE_BYTES;
+    const int nxt = slot == 2 ? 0 : slot + 1;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); T256_SB
+    RW_GROUP_READING(0, 1, so, )
+    // stage kt + 1 has landed once only stage kt + 2 is outstanding; past the barrier every wave has read all of stage kt, whose
+    // slot takes stage kt + 3
+    if (kt + 2 < nkt) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    T256_SB
+    const unsigned son = (unsigned)nxt * STAGE_BYTES;
+    const bool fetch = kt + 3 < nkt;
+    RW_GROUP_READING(1, 0, son, if (fetch) stage((kt + 3) * ROWS_BK, slot); T256_SB)
+    slot = nxt;
+  }
+  {          // the last stage: nothing left to wait for or to fetch
+    const unsigned so = (unsigned)slot * STAGE_BYTES;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); T256_SB
+    RW_GROUP_READING(0, 1, so, )
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); T256_SB
+    T256_GROUP(RW_MM, 1)
+  }
+#undef RW_RA
+#undef RW_RB
+#undef RW_MM
+#undef RW_GROUP_READING
+  __syncthreads();                                   // every wave has read its last fragments: the ring is free
+
+  // ---------------- epilogue: acc[i][j][r] = C[m0 + wm * 64 + i * 32 + acc_row(r, lh)][wn * 128 + j * 32 + l31] ----------------
+  float* cs = reinterpret_cast<float*>(lds2);        // [32][ROWS_CS_LD]
+  float4 gm[2], dg[2];
+#pragma unroll
+  for (int i = 0; i < 2; i++) { gm[i] = *reinterpret_cast<const float4*>(gamma + (lane + 64 * i) * 4); dg[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
+  const float inv_cols = 1.f / (float)ROWS_N;
+  // x, the residual, dx and its copy are streamed once: non-temporal, so that they do not evict B (up to 2.9 MiB, re-read by every
+  // workgroup) from the L2
+  auto ld4 = [](const float* p) { const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)); return make_float4(t[0], t[1], t[2], t[3]); };
+  auto st4 = [](float* p, const float4& o) { __builtin_nontemporal_store(f32x4{o.x, o.y, o.z, o.w}, reinterpret_cast<f32x4*>(p)); };
+  auto st4b = [](u16* p, const float4& o) { const uint2 pk = ln_pack4bf(o); __builtin_nontemporal_store(u32x2v{pk.x, pk.y}, reinterpret_cast<u32x2v*>(p)); };
+#pragma unroll
+  for (int p = 0; p < 4; p++) {
+    const int bi = p >> 1, half = p & 1;
+    // this wave's four rows of the pass, two pairs q of consecutive rows of C.  Their x and residual are requested before the tile
+    // goes through LDS (rows past M clamped: loaded, never used), so they travel under the LDS pass and its two barriers.
+    // Not a race in the in-place case (dx == residual): a clamped load reads row M - 1, which the wave owning that row may be
+    // storing at the same moment, but the loop below skips every row past M, so what such a load returned is never looked at.
+    // A row below M is loaded here and stored below by the same wave, the loads first.
+    float4 xq[2][2][2], rq[2][2][2];          // [q][row a / b][i]
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      const int lr = wave * 4 + q * 2;
+      const int mrow = m0 + (lr >> 4) * 64 + bi * 32 + half * 16 + (lr & 15);
+      const int64_t r0 = mrow < M ? mrow : M - 1, r1 = mrow + 1 < M ? mrow + 1 : r0;
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        const int c = (lane + 64 * i) * 4;
+        xq[q][0][i] = ld4(x + r0 * ldx + c); xq[q][1][i] = ld4(x + r1 * ldx + c);
+        if (residual) { rq[q][0][i] = ld4(residual + r0 * ldres + c); rq[q][1][i] = ld4(residual + r1 * ldres + c); }
+        else { rq[q][0][i] = make_float4(0.f, 0.f, 0.f, 0.f); rq[q][1][i] = make_float4(0.f, 0.f, 0.f, 0.f); }
+      }
+    }
+    if (p) __syncthreads();                          // the previous pass has been read
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+      for (int rr = 0; rr < 8; rr++) cs[(wm * 16 + acc_row(rr, lh)) * ROWS_CS_LD + wn * 128 + j * 32 + l31] = acc[bi][j][half * 8 + rr];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      const int lr = wave * 4 + q * 2;                // rows lr, lr + 1 of the pass
+      const int mrow = m0 + (lr >> 4) * 64 + bi * 32 + half * 16 + (lr & 15);
+      if (mrow >= M) continue;
+      const bool two = mrow + 1 < M;
+      const int64_t r0 = mrow, r1 = two ? r0 + 1 : r0;
+      const float* ca = cs + lr * ROWS_CS_LD;
+      const float* cb = cs + (two ? lr + 1 : lr) * ROWS_CS_LD;
+      float4 xa[2], xb[2], da[2], db[2];
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        const int c = (lane + 64 * i) * 4;
+        xa[i] = xq[q][0][i]; da[i] = *reinterpret_cast<const float4*>(ca + c);
+        xb[i] = xq[q][1][i]; db[i] = *reinterpret_cast<const float4*>(cb + c);
+      }
+      if (residual) {                                 // dy = A.B^T + residual, the add of the plain GEMM's epilogue
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+          const float4 ta = rq[q][0][i], tb = rq[q][1][i];
+          da[i].x += ta.x; da[i].y += ta.y; da[i].z += ta.z; da[i].w += ta.w;
+          db[i].x += tb.x; db[i].y += tb.y; db[i].z += tb.z; db[i].w += tb.w;
+        }
+      }
+      const float ma = mean_in[r0], ra = rstd_in[r0], mb = mean_in[r1], rb = rstd_in[r1];
+      float s1a, s2a, s1b, s2b;
+      ln_bwd_rows_stats<2>(xa, xb, da, db, gm, dg, ma, ra, mb, rb, two, inv_cols, s1a, s2a, s1b, s2b);
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        const int c = (lane + 64 * i) * 4;
+        float4 o = ln_bwd_row_dx(da[i], xa[i], ra, s1a, s2a);
+        st4(dx + r0 * lddx + c, o);
+        st4b(dx_bf16 + r0 * ld_bf16 + c, o);
+        if (two) {
+          o = ln_bwd_row_dx(db[i], xb[i], rb, s1b, s2b);
+          st4(dx + r1 * lddx + c, o);
+          st4b(dx_bf16 + r1 * ld_bf16 + c, o);
+        }
+      }
+    }
+  }
+  // block reduction of the dgamma partials through LDS, then one atomic per column and workgroup
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 2; i++) *reinterpret_cast<float4*>(cs + wave * ROWS_N + (lane + 64 * i) * 4) = dg[i];
+  __syncthreads();
+  float t = cs[tid];
+#pragma unroll
+  for (int w = 1; w < 8; w++) t += cs[w * ROWS_N + tid];
+  if (t != 0.f) atomicAdd(dgamma + tid, t);
+}
+
 // (the entry points of these kernels: end of file, after the weight-gradient kernels)
 
 // =====================================================================================================
@@ -1342,6 +1536,23 @@ extern "C" int mca_gemm_nt_lnres(const uint16_t* A, int64_t lda, const uint16_t*
   return launch(mca_plan_gemm_nt_lnres(M, N), o, stream);
 }
 
+// LayerNorm backward of dy = A·B^T (+ residual) in the epilogue of the full-row kernel: dy is never written (include/mca_hip.h).
+extern "C" int mca_gemm_nt_res_lnbwd(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* residual, int64_t ldres,
+                                     const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
+                                     float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16, float* dgamma,
+                                     int64_t M, int64_t N, int64_t K, mca_stream_t stream) {
+  if (!A || !B || !x || !mean || !rstd || !gamma || !dx || !dx_bf16 || !dgamma || M <= 0 || N <= 0 || K <= 0) return MCA_E_BADARG;
+  const int refusal = mca_nt_rows_refusal(M, N, K);
+  if (refusal) return refusal;
+  if (lda % 8 || ldb % 8 || ldx % 4 || lddx % 4 || ld_bf16 % 8 || (residual && ldres % 4) || (uintptr_t)A % 16 || (uintptr_t)B % 16 ||
+      (uintptr_t)x % 16 || (uintptr_t)gamma % 16 || (uintptr_t)dx % 16 || (uintptr_t)dx_bf16 % 16 || (uintptr_t)residual % 16)
+    return MCA_E_ALIGN;
+  if (lda < K || ldb < K || ldx < N || lddx < N || ld_bf16 < N || (residual && ldres < N)) return MCA_E_BADARG;
+  const mca_gemm_plan p = mca_plan_gemm_nt_res_lnbwd(M);
+  return launch_kernel<gemm_nt_rows_kernel>(p, stream, A, lda, B, ldb, residual, ldres, x, ldx, mean, rstd, gamma, dx, lddx, dx_bf16, ld_bf16,
+                                               dgamma, (int)M, (int)K, p.nwg);
+}
+
 // dh = GEGLU'(h) applied to dg = A·B^T without materialising dg (fused epilogue).  A[M,K] (= d x_out, bf16), B[ip,K] (= W2^T
 // copy), h / dh [M, 2*ip] bf16.
 // (saved: h holds the forward's saved factors s, include/mca_hip.h)
@@ -1535,6 +1746,10 @@ extern "C" int mca_dbg_plan_gemm_nt(int entry, const mca_nt_problem* pr, int cus
     case 3: *out = mca_plan_gemm_nt_geglu_bwd(pr->M, pr->N, pr->K, mca_knobs, cus); return MCA_OK;
     case 4: *out = mca_plan_gemm_nt_geglu_fwd_saved(pr->M, pr->N, pr->K, mca_knobs, cus); return MCA_OK;
     case 5: *out = mca_plan_gemm_nt_geglu_bwd_saved(pr->M, pr->N, pr->K, mca_knobs, cus); return MCA_OK;
+    case 6:
+      if (pr->M <= 0 || pr->N <= 0 || pr->K <= 0) return MCA_E_BADARG;
+      if (mca_nt_rows_refusal(pr->M, pr->N, pr->K)) return mca_nt_rows_refusal(pr->M, pr->N, pr->K);
+      *out = mca_plan_gemm_nt_res_lnbwd(pr->M); return MCA_OK;
   }
   return MCA_E_BADARG;
 }

@@ -49,7 +49,10 @@ enum mca_gemm_kernel {
   MCA_GK_NT_256_GEGLU_BWD_SAVED = MCA_GK_SAVED + MCA_GK_NT_256_GEGLU_BWD,                // gemm_nt_256_kernel<true, 0, 0, 3>
   MCA_GK_NT_PERSIST_GEGLU_BWD_SAVED = MCA_GK_SAVED + MCA_GK_NT_PERSIST_GEGLU_BWD,        // gemm_nt_persist_kernel<5, false>
   MCA_GK_NT_PERSIST_GEGLU_FWD_SAVED = MCA_GK_SAVED + MCA_GK_NT_PERSIST_GEGLU_FWD,        // gemm_nt_persist_kernel<6, false>
-  MCA_GK_NT_PERSIST256_GEGLU_FWD_SAVED = MCA_GK_SAVED + MCA_GK_NT_PERSIST256_GEGLU_FWD   // gemm_nt_persist256_kernel<true, true>
+  MCA_GK_NT_PERSIST256_GEGLU_FWD_SAVED = MCA_GK_SAVED + MCA_GK_NT_PERSIST256_GEGLU_FWD,  // gemm_nt_persist256_kernel<true, true>
+  // The full-row form (mca_gemm_nt_res_lnbwd): a workgroup owns whole rows of C and runs the LayerNorm backward's row body on
+  // them.  Outside the counted table like the saved forms.
+  MCA_GK_NT_ROWS_LNBWD = 128                                                              // gemm_nt_rows_kernel
 };
 
 // the instantiation a value stands for, spelled as in gemm.hip without blanks
@@ -73,6 +76,7 @@ static inline const char* mca_gemm_kernel_name(int k) {
     case MCA_GK_NT_PERSIST_GEGLU_BWD_SAVED: return "gemm_nt_persist_kernel<5,false>";
     case MCA_GK_NT_PERSIST_GEGLU_FWD_SAVED: return "gemm_nt_persist_kernel<6,false>";
     case MCA_GK_NT_PERSIST256_GEGLU_FWD_SAVED: return "gemm_nt_persist256_kernel<true,true>";
+    case MCA_GK_NT_ROWS_LNBWD: return "gemm_nt_rows_kernel";
   }
   return k >= 0 && k < MCA_GK_COUNT ? names[k] : "?";
 }
@@ -217,6 +221,35 @@ static inline mca_gemm_plan mca_plan_gemm_nt_geglu_fwd_saved(int64_t M, int64_t 
 }
 static inline mca_gemm_plan mca_plan_gemm_nt_geglu_bwd_saved(int64_t M, int64_t N, int64_t K, const int* knobs, int cus) {
   return mca_plan_saved(mca_plan_gemm_nt_geglu_bwd(M, N, K, knobs, cus));
+}
+
+// ---- the full-row kernel (gemm_nt_rows_kernel): a workgroup computes ROWS_BM whole rows of C[M, ROWS_N] in k-steps of ROWS_BK
+// through a ring of ROWS_NSTAGE stages of (A image [128][32], B image [512][32]); its epilogue moves the tile through the same LDS
+// 32 rows at a time (row stride ROWS_CS_LD floats: + 4 so that the accumulator rows of the two lane halves, 4 rows apart, fall
+// into different banks) and runs a LayerNorm row body on whole rows.
+#define ROWS_BM 128
+#define ROWS_N 512
+#define ROWS_BK 32
+#define ROWS_NSTAGE 3
+#define ROWS_STAGE ((ROWS_BM + ROWS_N) * ROWS_BK)          // elements per stage
+#define ROWS_CS_LD (ROWS_N + 4)
+#define ROWS_LDS_BYTES (ROWS_NSTAGE * ROWS_STAGE * 2)      // 120 KiB; the epilogue's 32 x ROWS_CS_LD floats (64.5 KiB) fit inside
+#define MCA_NT_ROWS_MIN_K (ROWS_NSTAGE * ROWS_BK)          // the prologue fills every stage of the ring
+
+// mca_gemm_nt_res_lnbwd: one workgroup per 128 rows, any M >= 1 (rows past M are clamped on load and never stored).  < 0: the
+// MCA_E_* code the entry point refuses the shape with (-3 = MCA_E_UNSUPPORTED, -2 = MCA_E_ALIGN).
+static inline int mca_nt_rows_refusal(int64_t M, int64_t N, int64_t K) {
+  if (N != ROWS_N || M > (1LL << 30)) return -3;
+  if (K % ROWS_BK) return -2;
+  if (K < MCA_NT_ROWS_MIN_K) return -3;
+  return 0;
+}
+static inline mca_gemm_plan mca_plan_gemm_nt_res_lnbwd(int64_t M) {
+  mca_gemm_plan pl = {};
+  pl.kernel = MCA_GK_NT_ROWS_LNBWD;
+  pl.n = ROWS_N; pl.tiles_n = 1; pl.nwg = (int)((M + ROWS_BM - 1) / ROWS_BM);
+  pl.grid_x = pl.nwg; pl.grid_y = 1; pl.block = 512; pl.lds_bytes = ROWS_LDS_BYTES;
+  return pl;
 }
 
 // ======================================================================================================================

@@ -52,9 +52,11 @@ def debug_options() -> dict:
     from the textbook form over 8 data seeds, profiles/r05_lazy_softmax_seed_study.txt), deterministic=1 (the fixed-order forms of
     the weight-gradient, LayerNorm-backward, row-reduction and table-gradient launches: FusionEngine.set_deterministic),
     geglu_saved=0 (the FF1 GEMM keeps h = [a | gate] and the backward evaluates gelu again, instead of the saved factors:
-    FusionEngine.geglu_saved_factors).  Kernel-level knobs: include/mca_hip_debug.h (hip.knobs)."""
+    FusionEngine.geglu_saved_factors), ln_rows=0 (the trunk LayerNorm backward as a launch of its own behind the data-gradient
+    GEMM instead of in that GEMM's full-row epilogue: FusionEngine.fuse_ln_rows).  Kernel-level knobs: include/mca_hip_debug.h
+    (hip.knobs)."""
     opts = {"overlap_wgrad": None, "group_wgrad": True, "mask_mfma": True, "dkv_keys": 128, "lazy_softmax": True,
-            "onepass": None, "deterministic": False, "geglu_saved": True}          # onepass=0|1: the one-pass attention backward (attention_bwd1.hip); default: by size
+            "onepass": None, "deterministic": False, "geglu_saved": True, "ln_rows": True}          # onepass=0|1: the one-pass attention backward (attention_bwd1.hip); default: by size
     for item in filter(None, os.environ.get("MCA_DEBUG", "").split(",")):
         k, _, v = item.partition("=")
         k = k.strip()
@@ -126,6 +128,9 @@ class FusionEngine:
         self.geglu_saved_factors = bool(self.dbg["geglu_saved"])
         self._mod_shifts = torch.arange(len(model.modality_types), dtype=torch.int32, device=self.device)
         self.fuse_ln_residual = True                # residual LayerNorm recomputed in the GEMM epilogue (large batches)
+        # The trunk LayerNorm backward inside the data-gradient GEMM that produces its dy (mca_gemm_nt_res_lnbwd: a workgroup owns
+        # whole rows, dy never reaches memory).  Where it applies: ln_rows_backward.
+        self.fuse_ln_rows = bool(self.dbg["ln_rows"])
         # Weight-gradient GEMMs on a side stream, concurrent with the backward chain: None = by size (on below OVERLAP_ROWS_MAX
         # token rows).  Since the attention backward lost its atomics the main stream keeps every CU busy and the persistent
         # weight-gradient GEMMs of a second stream only take CUs from it (one box, alternating processes: 23.7 / 25.6 ms per
@@ -711,6 +716,29 @@ class FusionEngine:
         bits = ((present[:, None] >> self._mod_shifts) & 1).to(torch.bool)          # (b, M): one small op for every modality
         return {name: bits[:, mi] for mi, name in enumerate(m.modality_types)}
 
+    def ln_in_gemm(self, T: int) -> bool:
+        """the residual LayerNorm recomputed in the out-proj / FF2 GEMM epilogues: what mca_gemm_nt_lnres accepts"""
+        return self.fuse_ln_residual and T >= 2048 and self.D % 128 == 0 and self.D >= 512 and self.Ip >= 512
+
+    def ln_rows_backward(self, T: int) -> bool:
+        """The rule for the fused data-gradient GEMM + LayerNorm backward (mca_gemm_nt_res_lnbwd) in place of the pair mca_gemm_nt +
+        mca_layernorm_bwd: the large-batch path (ln_in_gemm) of the MCA model at the one width the full-row kernel is built for, and
+        never in deterministic mode, whose LayerNorm backward adds dgamma in a fixed order (mca_layernorm_bwd_det).  All three
+        data-gradient shapes of the step (K = 2 Ip, 3 D, 2 D) take it: profiles/ln_rows_fusion.md has each against its pair."""
+        return self.fuse_ln_rows and self.ln_in_gemm(T) and self.D == 512 and not self._deterministic and not self.eao
+
+    def _gemm_ln_bwd(self, A, B, K, residual, x, gamma, mean, rstd, dgamma, dx, dx_bf16, T):
+        """dx (fp32, may be the residual), dx_bf16, dgamma += : the LayerNorm backward of dy = A B^T (+ residual) in one launch; timed
+        under the row of the GEMM it replaces"""
+        D = self.D
+        if hip.PROFILE is not None:
+            hip.set_tag(f"{T}x{D}x{K} f32{' +res' if residual is not None else ''}")
+        call("mca_gemm_nt_res_lnbwd", ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(residual), residual.stride(0) if residual is not None else 0,
+             ptr(x), x.stride(0), ptr(mean), ptr(rstd), ptr(gamma), ptr(dx), dx.stride(0), ptr(dx_bf16), dx_bf16.stride(0), ptr(dgamma),
+             T, D, K, stream_ptr(), flops=2.0 * T * D * K, profile_as="mca_gemm_nt")
+        if hip.PROFILE is not None:
+            hip.set_tag("")
+
     def forward_trunk(self, ws):
         """fusion layers + final norm + attentive pooling -> ws['pooled'] (b*R, D)."""
         m, D, N, H, Ip, R, b, T = self.model, self.D, self.N, self.H, self.Ip, self.R, ws["b"], ws["T"]
@@ -720,7 +748,7 @@ class FusionEngine:
             call("mca_build_keyhot", ptr(ws["keyinfo"]), ptr(ws["khot"]), b, self.nk_pad, stream_ptr())
         # T >= 2048: the residual LayerNorm(x) is recomputed inside the out-proj / FF2 GEMM epilogues from x and the saved row
         # statistics (mca_gemm_nt_lnres): the LayerNorm kernels then write the bf16 GEMM operand only
-        ln_in_gemm = self.fuse_ln_residual and T >= 2048 and D % 128 == 0 and D >= 512 and Ip >= 512
+        ln_in_gemm = self.ln_in_gemm(T)
         saved = self.geglu_saved_factors and self.fuse_geglu_bwd
         ff1 = "mca_gemm_nt_geglu_fwd_saved" if saved else "mca_gemm_nt_geglu_fwd"
         for i, ly in enumerate(m.layers):
@@ -938,9 +966,13 @@ class FusionEngine:
             on_side(lambda pk=pool_kv: tn(pk[0], pk[1], pk[2], T, 2 * D, D))
             pool_kv = None
         dx, dx_other = ws["dxa"], ws["dxb"]
-        self.gemm_nt(ws["dkvp"], self.wp["kvT"], dx, T, D, 2 * D)                    # d (final-normed tokens), fp32
         top = ws["layers"][self.L - 1]["dxo_b"] if self.L else ws["dx_b"]
-        self._ln_bwd(ws, dx, D, ws["x"][self.L], m.norm.gamma, ws["mf"], ws["rf"], T, D, G(m.norm.gamma), dx=dx_other, dx_bf16=top)
+        if self.ln_rows_backward(T):
+            self._gemm_ln_bwd(ws["dkvp"], self.wp["kvT"], 2 * D, None, ws["x"][self.L], m.norm.gamma, ws["mf"], ws["rf"], G(m.norm.gamma),
+                              dx_other, top, T)
+        else:
+            self.gemm_nt(ws["dkvp"], self.wp["kvT"], dx, T, D, 2 * D)                    # d (final-normed tokens), fp32
+            self._ln_bwd(ws, dx, D, ws["x"][self.L], m.norm.gamma, ws["mf"], ws["rf"], T, D, G(m.norm.gamma), dx=dx_other, dx_bf16=top)
         dx, dx_other = dx_other, dx
         on_side(lambda: bucket_ready(0))
         self._backward_layers_and_encoders(ws, dx, dx_other, bucket_ready, on_side, extra_top=pool_kv)
@@ -988,8 +1020,12 @@ class FusionEngine:
             gw1 = G(ly.ff.feedforward[0].weight)
             if not grouped:
                 on_side(lambda dh=dh, a=a, gw1=gw1: (tn(dh, a["x1n_b"], gw1, T, I, D), tn(dh[:, Ip:], a["x1n_b"], gw1[I:], T, I, D)))
-            self.gemm_nt(dh, w["w1T"], dx_other, T, D, 2 * Ip, residual=dx)            # d x1n = dh @ W1 + dx
-            self._ln_bwd(ws, dx_other, D, a["x1"], g, a["m2"], a["r2"], T, D, G(g), dx=dx, dx_bf16=dx1)   # dx = d x1
+            rows = self.ln_rows_backward(T)          # d x1n / d xn stay in the GEMM's tile; dx is read (residual) and written in place
+            if rows:
+                self._gemm_ln_bwd(dh, w["w1T"], 2 * Ip, dx, a["x1"], g, a["m2"], a["r2"], G(g), dx, dx1, T)
+            else:
+                self.gemm_nt(dh, w["w1T"], dx_other, T, D, 2 * Ip, residual=dx)            # d x1n = dh @ W1 + dx
+                self._ln_bwd(ws, dx_other, D, a["x1"], g, a["m2"], a["r2"], T, D, G(g), dx=dx, dx_bf16=dx1)   # dx = d x1
             # x1 = o @ Wo^T + xn
             if not grouped:
                 on_side(lambda dx1=dx1, a=a, ly=ly: tn(dx1, a["o"], G(ly.attn.to_out.weight), T, D, D))
@@ -1007,8 +1043,11 @@ class FusionEngine:
                      (dxo, a["g"], gw2, D, I), (dx1, a["o"], gwo, D, D)] + extra, T))
             else:
                 on_side(lambda dqkv=dqkv, a=a, gq=gq: tn(dqkv, a["xn_b"], gq, T, 3 * D, D))
-            self.gemm_nt(dqkv, w["qkvT"], dx_other, T, D, 3 * D, residual=dx)          # d xn = dqkv @ Wqkv + d x1
-            self._ln_bwd(ws, dx_other, D, ws["x"][i], g, a["m1"], a["r1"], T, D, G(g), dx=dx, dx_bf16=below)  # dx = d x_in
+            if rows:
+                self._gemm_ln_bwd(dqkv, w["qkvT"], 3 * D, dx, ws["x"][i], g, a["m1"], a["r1"], G(g), dx, below, T)
+            else:
+                self.gemm_nt(dqkv, w["qkvT"], dx_other, T, D, 3 * D, residual=dx)          # d xn = dqkv @ Wqkv + d x1
+                self._ln_bwd(ws, dx_other, D, ws["x"][i], g, a["m1"], a["r1"], T, D, G(g), dx=dx, dx_bf16=below)  # dx = d x_in
             on_side(lambda bi=bi: bucket_ready(bi + 1))
         # dx = gradient w.r.t. the packed encoder output (b, N, D)
         if self.eao:          # the gradients of a modality's replicas, summed into the segment its encoder wrote

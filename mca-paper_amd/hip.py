@@ -163,6 +163,8 @@ class TnGroupDetPlan(C.Structure):
 
 PLAN_NT, PLAN_LNRES, PLAN_GEGLU_FWD, PLAN_GEGLU_BWD, PLAN_GEGLU_FWD_SAVED, PLAN_GEGLU_BWD_SAVED = range(6)          # `entry` of mca_dbg_plan_gemm_nt
 GK_SAVED = 64          # csrc/gemm_plan.h MCA_GK_SAVED: a saved-factor kernel's value is its unsaved sibling's + this
+PLAN_RES_LNBWD = 6     # mca_gemm_nt_res_lnbwd
+GK_NT_ROWS_LNBWD = 128          # csrc/gemm_plan.h MCA_GK_NT_ROWS_LNBWD: gemm_nt_rows_kernel
 
 
 # the LayerNorm planners' structs (csrc/ln_plan.h; filled by mca_dbg_plan_layernorm_fwd / _bwd).  Pointers travel as integers.
@@ -206,6 +208,8 @@ SIGNATURES = {
     # saved-factor forms: the siblings' argument lists, s in the place of h
     "mca_gemm_nt_geglu_fwd_saved": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
     "mca_gemm_nt_geglu_bwd_saved": (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P]),
+    # full-row GEMM + LayerNorm backward: A, lda, B, ldb, residual, ldres, x, ldx, mean, rstd, gamma, dx, lddx, dx_bf16, ld_bf16, dgamma, M, N, K
+    "mca_gemm_nt_res_lnbwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P]),
     "mca_geglu_fwd_saved": (_I, [_P, _P, _I64, _I, _P]),
     "mca_geglu_bwd_saved": (_I, [_P, _P, _P, _I64, _I, _P]),
     "mca_gemm_tn_acc": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
