@@ -42,6 +42,14 @@ int mca_gemm_nt(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb,
                 const float* bias, const float* residual, int64_t ldres, int64_t res_period,
                 int64_t M, int64_t N, int64_t K, mca_stream_t stream);
 
+/* The same product, bf16, stored COLUMN-BLOCKED: column n of row m at C + (n / 64) * cbs + m * 64 + n % 64, i.e. N / 64 slabs of
+ * [M][64], cbs >= M * 64 elements apart - the head-major form the attention kernels read in place (mca_attn_layout).  Exactly the
+ * values mca_gemm_nt writes for the same operands; nothing outside rows 0 .. M - 1 of a slab is touched.  Shapes of the 256 x 256
+ * persistent kernel only: M >= 2048, N % 256 == 0, K >= 192, K % 32 == 0, C % 16 == 0, cbs % 8 == 0 (MCA_E_UNSUPPORTED otherwise:
+ * the caller keeps mca_gemm_nt and the row-major layout; mca_dbg_plan_gemm_nt_cb answers without a launch).                     */
+int mca_gemm_nt_cb(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t cbs,
+                   int64_t M, int64_t N, int64_t K, mca_stream_t stream);
+
 /* C[M,N] (fp32) = A[M,K]·B[N,K]^T + LayerNorm(x)[M,N], the LayerNorm (model.py:24-31, beta = 0) recomputed in the epilogue
  * as (x - mean[m]) * rstd[m] * gamma[n] from the saved pre-norm tensor and the statistics mca_layernorm_fwd wrote: the
  * residual branches x = Attn(LN(x)) + LN(x), x = FF(LN(x)) + LN(x) of MCALayer.forward (model.py:117-122) without the normed
@@ -330,6 +338,17 @@ typedef struct {
 /* dim_head is fixed at 64; query tile 128 rows, key tile 64.                                     */
 int mca_attn_fwd(const mca_attn_fwd_args* args, mca_stream_t stream);
 
+/* Where the heads of q and of k | v lie, for operands that are not (rows, heads*64) matrices: head h starts q_hstride (kv_hstride)
+ * elements behind head 0, 0 = 64.  The column-blocked output of mca_gemm_nt_cb, [block][T][64] with cbs elements between the blocks,
+ * is q_bstride = kv_bstride = n*64, q_ld = kv_ld = 64, q_hstride = kv_hstride = cbs, with q, k and v pointing at blocks 0, heads and
+ * 2*heads: a (sample, head) is then n contiguous 128-byte rows.  Strides % 8 == 0.  The argument structs above and below keep their
+ * fields: the layout travels beside them.                                                                                        */
+typedef struct { int64_t q_hstride, kv_hstride; } mca_attn_layout;
+/* mca_attn_fwd / mca_attn_vmean_if_needed on such operands (layout NULL or all zero: exactly those calls; same kernels, same bits) */
+int mca_attn_fwd_hm(const mca_attn_fwd_args* args, const mca_attn_layout* layout, mca_stream_t stream);
+int mca_attn_vmean_if_needed_hm(const uint16_t* V, int64_t kv_bstride, int64_t kv_ld, int64_t kv_hstride, float* vmean, int batch, int nk,
+                                int heads, const int32_t* present, int32_t full_bits, mca_stream_t stream);
+
 /* Attention READOUT (model.py:87-103: Attention.forward with return_attn=True returns softmax(q·k^T) after its two
  * masked_fill; here the (b, h, nq, nk) matrix is never written).  One launch per attention, after mca_attn_fwd on the same
  * operands (same conventions: head = 64 contiguous bf16, q_bstride 0 for the pooling query, MCA_ATTN_Q_PRESCALED required,
@@ -497,6 +516,16 @@ int mca_attn_bwd_prep_onepass(const uint16_t* o, const uint16_t* d_o, int64_t o_
                               const int32_t* row_slot, float* rowc, float* dvmean, int batch, int heads, int n, int n_qtiles,
                               const uint16_t* q, int64_t q_bstride, int64_t q_ld, uint16_t* q_hm, uint16_t* do_hm,
                               mca_stream_t stream);
+/* The one-pass backward on head-major operands that need no packed copies: q and d_o as written by mca_gemm_nt_cb (the struct's own
+ * q_hstride / o_hstride say so already), k | v through layout->kv_hstride (q_hstride of the layout is not read).  layout NULL or
+ * zero: mca_attn_bwd_onepass.  The slack rule of the packed copies holds for the buffers q and d_o lie in: 64 finite rows behind the
+ * last slab that is read as q or d_o (a tile's over-read inside the buffer lands in the next sample or slab).                   */
+int mca_attn_bwd_onepass_hm(const mca_attn_bwd1_args* args, const mca_attn_layout* layout, mca_stream_t stream);
+/* Its prep launch: rowc and dvmean as mca_attn_bwd_prep_onepass writes them (delta summed by the same lanes in the same order: the
+ * same bits), o row-major, d_o[b*do_bstride + head*do_hstride + i*do_ld + d] (do_hstride 0 = 64), and no copy of anything.      */
+int mca_attn_bwd_prep_onepass_hm(const uint16_t* o, int64_t o_bstride, int64_t o_ld, const uint16_t* d_o, int64_t do_bstride,
+                                 int64_t do_hstride, int64_t do_ld, const float* lse, const int32_t* row_slot, float* rowc,
+                                 float* dvmean, int batch, int heads, int n, int n_qtiles, mca_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * All-pairs contrastive loss with temperature

@@ -51,6 +51,10 @@ int mca_dbg_plan_gemm_nt(int entry, const struct mca_nt_problem* problem, int cu
 int mca_dbg_plan_gemm_tn(int64_t R, int64_t N, int64_t K, struct mca_gemm_plan* out);
 int mca_dbg_plan_gemm_tn_group(const int64_t* N, const int64_t* K, int n, int64_t R, int cus, struct mca_tn_group_plan* out);
 const char* mca_dbg_gemm_kernel_name(int kernel);
+/* mca_gemm_nt_cb's plan for a C at address `C` with slab stride cbs: mca_gemm_nt's plan for the same shape with the column-blocked
+ * kernel, or MCA_E_UNSUPPORTED where the entry point refuses (the current knob table included).  cus > 0 touches no device: the
+ * engine asks with it before it chooses a layout. */
+int mca_dbg_plan_gemm_nt_cb(int64_t M, int64_t N, int64_t K, uint64_t C, int64_t cbs, int cus, struct mca_gemm_plan* out);
 /* The plans of the deterministic weight-gradient forms (mca_gemm_tn_acc_det, mca_gemm_tn_acc_group_det; structs in csrc/gemm_plan.h):
  * the launch, the slot count, the slot stride and the scratch floats, with the current knob table. */
 struct mca_tn_det_plan;

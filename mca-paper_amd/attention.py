@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .hip import AttnBwd1Args, AttnBwd2Args, AttnFwdArgs, AttnReadoutArgs, call, stream_ptr
+from .hip import AttnBwd1Args, AttnBwd2Args, AttnFwdArgs, AttnLayout, AttnReadoutArgs, call, stream_ptr
 
 ONEPASS_MIN_WG = 192          # (sample, head) pairs from which the one-pass backward is the default: one workgroup per CU
 
@@ -71,6 +71,9 @@ class AttnOperands(NamedTuple):
     sched_f: Any                # _Sched of the forward and dq pass
     sched_b: Any                # _Sched of the dkv pass
     layer: Optional[int]        # fusion layer (its fp8 operand cache); None: the pooling attention
+    hstride: int = 0            # elements between the heads of q and of k | v; 0: the 64-column blocks of a row.  The head-major
+                                # output of mca_gemm_nt_cb ([block][T][64], slabs cbs apart): q_bstride = nk * 64, q_ld = kv_ld = 64,
+                                # k_off = H * cbs, v_off = 2 * H * cbs, hstride = cbs; only the _hm entry points take it
 
 
 class AttnGrads(NamedTuple):
@@ -85,6 +88,7 @@ class AttnGrads(NamedTuple):
     dk_off: int
     dv_off: int
     dkv_ld: int
+    do_hstride: int = 0         # d_o written head-major by mca_gemm_nt_cb: d_o[(sample * nq + row) * 64 + head * do_hstride + d]
 
 
 class AttnKeys(NamedTuple):
@@ -122,6 +126,11 @@ def _shared(a, ops, keys):
             a.qblk = ops.qblk.data_ptr()
     a.batch, a.heads, a.nk_pad, a.scale, a.flags = keys.batch, keys.heads, keys.nk_pad, keys.scale, keys.flags
     return a
+
+
+def layout_args(ops: AttnOperands) -> AttnLayout:
+    """the head strides of ops for the _hm entry points (zero: the plain entry points' layout)"""
+    return AttnLayout(ops.hstride, ops.hstride)
 
 
 def fwd_args(ops: AttnOperands, keys: AttnKeys, vmean: torch.Tensor) -> AttnFwdArgs:
@@ -192,6 +201,8 @@ def launch_forward(a: AttnFwdArgs, ops: AttnOperands, fp8=None):
     if fp8 is not None:
         call("mca_attn_quant_mxfp8", a.q, a.q_bstride, a.q_ld, a.k, a.v, a.kv_bstride, a.kv_ld, C.byref(fp8), a.batch, a.heads, a.nk, stream_ptr())
         call("mca_attn_fwd_fp8", C.byref(a), C.byref(fp8), stream_ptr(), flops=flops)
+    elif ops.hstride:
+        call("mca_attn_fwd_hm", C.byref(a), C.byref(layout_args(ops)), stream_ptr(), flops=flops, profile_as="mca_attn_fwd")
     else:
         call("mca_attn_fwd", C.byref(a), stream_ptr(), flops=flops)
     hip.set_tag("")
@@ -232,6 +243,23 @@ def backward_onepass(ops: AttnOperands, grads: AttnGrads, keys: AttnKeys, sched:
                   RowSource(q_hm.data_ptr(), H * n * 64, n * 64, 64), RowSource(do_hm.data_ptr(), H * n * 64, n * 64, 64))
     hip.set_tag("layer")
     call("mca_attn_bwd_onepass", C.byref(a), stream_ptr(), flops=8.0 * 64 * sched.s.allowed_pairs * H * b)
+    hip.set_tag("")
+
+
+def backward_onepass_hm(ops: AttnOperands, grads: AttnGrads, keys: AttnKeys, sched: "_OnePassSched", rowc: torch.Tensor,
+                        dq_acc: torch.Tensor, dvmean: torch.Tensor, split: int):
+    """backward_onepass on head-major operands (ops.hstride, grads.do_hstride: what mca_gemm_nt_cb wrote): the kernel reads q and
+    dO in place, the prep launch writes the row constants and dvmean only.  Timed under the entry points it replaces."""
+    assert ops.hstride and grads.do_hstride and ops.q_ld == 64 and ops.kv_ld == 64, "head-major operands only"
+    n, H, b, o = keys.nk, keys.heads, keys.batch, ops.o
+    call("mca_attn_bwd_prep_onepass_hm", o.data_ptr(), n * o.stride(0), o.stride(0), grads.d_o.data_ptr(), n * 64, grads.do_hstride, 64,
+         ops.lse.data_ptr(), sched.row_slot.data_ptr(), rowc.data_ptr(), dvmean.data_ptr(), b, H, n, sched.n_qt, stream_ptr(),
+         profile_as="mca_attn_bwd_prep_onepass")
+    a = bwd1_args(ops, grads, keys, sched, rowc, dq_acc, dvmean, split, RowSource(ops.q, ops.q_bstride, ops.hstride, 64),
+                  RowSource(grads.d_o.data_ptr(), n * 64, grads.do_hstride, 64))
+    hip.set_tag("layer")
+    call("mca_attn_bwd_onepass_hm", C.byref(a), C.byref(layout_args(ops)), stream_ptr(), flops=8.0 * 64 * sched.s.allowed_pairs * H * b,
+         profile_as="mca_attn_bwd_onepass")
     hip.set_tag("")
 
 

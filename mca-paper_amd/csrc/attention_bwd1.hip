@@ -38,7 +38,7 @@ __device__ __forceinline__ int b1_swz(int r) { return ((r >> 1) & 7) ^ (((r >> 1
 
 #define B1_DMA(SRC, DST, BYTES) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(SRC), (__attribute__((address_space(3))) void*)(DST), BYTES, 0, 0)
 
-__global__ __launch_bounds__(256, 1) void attn_bwd1_kernel(mca_attn_bwd1_args a, int dbg) {
+__global__ __launch_bounds__(256, 1) void attn_bwd1_kernel(mca_attn_bwd1_args a, int dbg, int64_t kv_hs) {          // kv_hs: elements between the heads of k | v (mca_attn_layout)
   extern __shared__ __attribute__((aligned(16))) u16 lds[];
   u16* stage_s = lds;                                             // B1_NST stages
   u16* kimg = stage_s + B1_NST * B1_STAGE_U16;                    // [256 keys][64 d]: A operand of the dQ product (transposed reads)
@@ -58,8 +58,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd1_kernel(mca_attn_bwd1_args a,
 
   const u16* qbase = a.q + (int64_t)b * a.q_bstride + h * (a.q_hstride ? a.q_hstride : (int64_t)DH);
   const u16* obase = a.d_o + (int64_t)b * a.o_bstride + h * (a.o_hstride ? a.o_hstride : (int64_t)DH);
-  const u16* kbase = a.k + (int64_t)b * a.kv_bstride + h * DH;
-  const u16* vbase = a.v + (int64_t)b * a.kv_bstride + h * DH;
+  const u16* kbase = a.k + (int64_t)b * a.kv_bstride + h * kv_hs;
+  const u16* vbase = a.v + (int64_t)b * a.kv_bstride + h * kv_hs;
   const float* rowc_g = a.rowc + bh * (int64_t)(a.n_qtiles + 1) * 128;          // (+ the null tile)
   float* acc_g = a.dq_acc + bh * (int64_t)(a.n_qtiles + 1) * (TQ * DH);          // (+ the null tile's slot: only the pipelined kernel writes it)
   const uint8_t* kinfo_g = a.keyinfo + (int64_t)b * a.nk_pad;
@@ -475,7 +475,7 @@ MCA_TRACE_BUFFER(attn_bwd1)      // trace build, knob 9 bit 8: s_memtime stamps 
 
 // (the body is a __device__ function: the host pass of hipcc checks the register constraints of inline asm in a __global__ body
 //  against the host's register classes)
-__device__ __forceinline__ void attn_bwd1p_body(const mca_attn_bwd1_args& a, const int dbg, u16* lds) {
+__device__ __forceinline__ void attn_bwd1p_body(const mca_attn_bwd1_args& a, const int dbg, const int64_t kv_hs, u16* lds) {
   u16* stage_s = lds;                                             // B1P_NST stages
   u16* kimg = stage_s + B1P_NST * B1_STAGE_U16;
   u16* dsimg = kimg + TKB * DH;
@@ -507,8 +507,8 @@ __device__ __forceinline__ void attn_bwd1p_body(const mca_attn_bwd1_args& a, con
 
   const u16* qbase = a.q + (int64_t)b * a.q_bstride + h * (a.q_hstride ? a.q_hstride : (int64_t)DH);
   const u16* obase = a.d_o + (int64_t)b * a.o_bstride + h * (a.o_hstride ? a.o_hstride : (int64_t)DH);
-  const u16* kbase = a.k + (int64_t)b * a.kv_bstride + h * DH;
-  const u16* vbase = a.v + (int64_t)b * a.kv_bstride + h * DH;
+  const u16* kbase = a.k + (int64_t)b * a.kv_bstride + h * kv_hs;
+  const u16* vbase = a.v + (int64_t)b * a.kv_bstride + h * kv_hs;
   const float* rowc_g = a.rowc + bh * (int64_t)(a.n_qtiles + 1) * 128;          // (+ the null tile)
   float* acc_s = a.dq_acc + (bh * S + sid) * (int64_t)(a.n_qtiles + 1) * (TQ * DH) + wave * 1024;          // (wave-uniform; lane l's slot at + 4 l)
   const uint8_t* kinfo_g = a.keyinfo + (int64_t)b * a.nk_pad;
@@ -1077,15 +1077,16 @@ __global__ __launch_bounds__(256) void attn_bwd1_reduce_kernel(mca_attn_bwd1_arg
     }
   }
 }
-__global__ __launch_bounds__(256, 1) void attn_bwd1p_kernel(mca_attn_bwd1_args a, int dbg) {
+__global__ __launch_bounds__(256, 1) void attn_bwd1p_kernel(mca_attn_bwd1_args a, int dbg, int64_t kv_hs) {
   extern __shared__ __attribute__((aligned(16))) u16 lds_dyn[];
-  attn_bwd1p_body(a, dbg, lds_dyn);
+  attn_bwd1p_body(a, dbg, kv_hs, lds_dyn);
 }
 #define B1P_LDS_BYTES ((B1P_NST * B1_STAGE_U16 + TKB * DH + 2 * TKB * TQ) * 2 + B1_MAX_META * 8 + B1_MAX_KB * 16 + B1_MAX_KB + DH * 4 + 16)
 
 #define B1_LDS_BYTES ((B1_NST * B1_STAGE_U16 + TKB * DH + 2 * TKB * TQ) * 2 + B1_MAX_LIST * 4 + 2 * B1_MAX_QT + B1_MAX_KB + DH * 4)
 
-extern "C" int mca_attn_bwd_onepass(const mca_attn_bwd1_args* a, mca_stream_t stream) {
+// every one-pass launch: mca_attn_bwd_onepass (a zero layout) and mca_attn_bwd_onepass_hm
+static int attn_bwd1_launch(const mca_attn_bwd1_args* a, const mca_attn_layout& lay, mca_stream_t stream) {
   if (!a || !a->q || !a->k || !a->v || !a->d_o || !a->rowc || !a->dvmean || !a->dq || !a->dk || !a->dv || !a->dq_acc) return MCA_E_BADARG;
   if (!a->keyinfo || !a->ktile_flags || !a->khot || !a->qblk || !a->qt_desc || !a->kb_desc || !a->kb_qt || !a->visit) return MCA_E_BADARG;
   if (a->batch <= 0 || a->heads <= 0 || a->n <= 0 || a->n_qtiles <= 0 || a->n_kblocks <= 0) return MCA_E_BADARG;
@@ -1098,6 +1099,8 @@ extern "C" int mca_attn_bwd_onepass(const mca_attn_bwd1_args* a, mca_stream_t st
   if (a->nk_pad < a->n || a->n_ktiles64 != (a->n + 63) / 64) return MCA_E_BADARG;
   if (!(a->flags & MCA_ATTN_Q_PRESCALED)) return MCA_E_UNSUPPORTED;
   if ((int64_t)a->batch * a->heads > 0x7fffffff) return MCA_E_UNSUPPORTED;
+  if (lay.kv_hstride % 8 || lay.kv_hstride < 0) return MCA_E_ALIGN;
+  const int64_t kv_hs = lay.kv_hstride ? lay.kv_hstride : (int64_t)DH;
   if (!mca_dyn_lds<attn_bwd1_kernel>(B1_LDS_BYTES) || !mca_dyn_lds<attn_bwd1p_kernel>(B1P_LDS_BYTES)) return MCA_E_LAUNCH;
   // knob 9 bit 64: the plain (compiler-scheduled) form of the same algorithm instead of the pipelined one (A/B and cross-check)
   // the pipelined kernel reads q / dO from the head-major packed copies only (64-element rows: a tile is 8 KiB contiguous)
@@ -1105,8 +1108,12 @@ extern "C" int mca_attn_bwd_onepass(const mca_attn_bwd1_args* a, mca_stream_t st
   const int split = a->split > 1 ? a->split : 1;
   if (split > 8) return MCA_E_UNSUPPORTED;
   if (split > 1 && !packed) return MCA_E_UNSUPPORTED;          // (split mode exists in the pipelined kernel only)
-  if ((mca_knobs[9] & 64 && split == 1) || !packed) hipLaunchKernelGGL(attn_bwd1_kernel, dim3(a->batch * a->heads), dim3(256), B1_LDS_BYTES, as_stream(stream), *a, mca_knobs[9]);
-  else hipLaunchKernelGGL(attn_bwd1p_kernel, dim3(a->batch * a->heads * split), dim3(256), B1P_LDS_BYTES, as_stream(stream), *a, mca_knobs[9]);
+  if ((mca_knobs[9] & 64 && split == 1) || !packed) hipLaunchKernelGGL(attn_bwd1_kernel, dim3(a->batch * a->heads), dim3(256), B1_LDS_BYTES, as_stream(stream), *a, mca_knobs[9], kv_hs);
+  else hipLaunchKernelGGL(attn_bwd1p_kernel, dim3(a->batch * a->heads * split), dim3(256), B1P_LDS_BYTES, as_stream(stream), *a, mca_knobs[9], kv_hs);
   if (split > 1) hipLaunchKernelGGL(attn_bwd1_reduce_kernel, dim3(a->n_qtiles, a->batch * a->heads), dim3(256), 0, as_stream(stream), *a);
   return launch_status();
+}
+extern "C" int mca_attn_bwd_onepass(const mca_attn_bwd1_args* a, mca_stream_t stream) { return attn_bwd1_launch(a, mca_attn_layout{0, 0}, stream); }
+extern "C" int mca_attn_bwd_onepass_hm(const mca_attn_bwd1_args* a, const mca_attn_layout* layout, mca_stream_t stream) {
+  return attn_bwd1_launch(a, layout ? *layout : mca_attn_layout{0, 0}, stream);
 }

@@ -665,9 +665,10 @@ __device__ __forceinline__ void attn_bwd_prep_block(const int bx, const int by, 
 // (a kernel, not hipMemsetAsync: as a memset NODE of a single-chain captured step the zeroing was not ordered against the
 // kernels around it - the whole backward then started from a dvmean full of stale sums).
 #define DVM_MAX_LIST 4096
+// (hs: elements between the heads of d_o - DH in the row-major matrix, the slab stride in the column-blocked form)
 __device__ __forceinline__ void attn_dvmean_block(const int bx, const int by, const u16* __restrict__ d_o, int64_t bstride, int64_t ld,
                                                   const float* __restrict__ lse, float* __restrict__ dvmean,
-                                                  int heads, int nq, float inv_nk) {
+                                                  int heads, int nq, float inv_nk, const int64_t hs) {
   __shared__ int list_s[DVM_MAX_LIST];
   __shared__ int n_s;
   __shared__ float red[32][DH + 1];
@@ -688,7 +689,7 @@ __device__ __forceinline__ void attn_dvmean_block(const int bx, const int by, co
   auto flush = [&]() {          // every thread, behind a barrier that made the list visible
     const int n = n_s;
     for (int i = rg; i < n; i += 32) {
-      const bf16x8 v = *reinterpret_cast<const bf16x8*>(d_o + (int64_t)b * bstride + (int64_t)list_s[i] * ld + h * DH + cl * 8);
+      const bf16x8 v = *reinterpret_cast<const bf16x8*>(d_o + (int64_t)b * bstride + (int64_t)list_s[i] * ld + h * hs + cl * 8);
 #pragma unroll
       for (int j = 0; j < 8; j++) acc[j] += bf2f((u16)v[j]);
     }
@@ -730,7 +731,7 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const u16* __restric
                                                              u16* __restrict__ q_hm, u16* __restrict__ do_hm) {
   if ((int)blockIdx.x < n_prep) attn_bwd_prep_block((int)blockIdx.x, (int)blockIdx.y, o, d_o, bstride, ld, delta, heads, nq, lse, row_slot, rowc, n_qtiles,
                                                     qsrc, q_bstride, q_ld, q_hm, do_hm);
-  else attn_dvmean_block((int)blockIdx.x - n_prep, (int)blockIdx.y, d_o, bstride, ld, lse, dvmean, heads, nq, inv_nk);
+  else attn_dvmean_block((int)blockIdx.x - n_prep, (int)blockIdx.y, d_o, bstride, ld, lse, dvmean, heads, nq, inv_nk, (int64_t)DH);
 }
 extern "C" int mca_attn_bwd_prep(const uint16_t* o, const uint16_t* d_o, int64_t o_bstride, int64_t o_ld,
                                  const float* lse, float* delta, float* dvmean, int batch, int heads, int nq, int nk,
@@ -756,5 +757,76 @@ extern "C" int mca_attn_bwd_prep_onepass(const uint16_t* o, const uint16_t* d_o,
   const int n_prep = (n + PREP_ROWS - 1) / PREP_ROWS;
   hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3(n_prep + heads, batch), dim3(256), 0, as_stream(stream), o, d_o, o_bstride, o_ld, lse, (float*)nullptr,
                      dvmean, heads, n, 1.f / (float)n, n_prep, row_slot, rowc, n_qtiles, q, q_bstride, q_ld, q_hm, do_hm);
+  return launch_status();
+}
+
+// =====================================================================================================
+// The one-pass prep on a dO whose heads lie do_hs elements apart (the column-blocked output of mca_gemm_nt_cb): the row constants
+// and dvmean only - q and dO are read where their GEMMs wrote them, nothing is copied.  attn_bwd_prep_block's rows, lanes and
+// sums: lane l of a row holds columns 8 l .. 8 l + 7 of a 512-column slab, i.e. chunk l & 7 of head l >> 3, and delta is added
+// over the 8 values of a lane and then over the 8 lanes of a head in the same order, so its bits are those of
+// mca_attn_bwd_prep_onepass.  (Its own lines, not a flag of attn_bwd_prep_block: the copies' registers stay out of this kernel.)
+// =====================================================================================================
+__global__ __launch_bounds__(256) void attn_bwd_prep_hm_kernel(const u16* __restrict__ o, int64_t o_bstride, int64_t o_ld,
+                                                                const u16* __restrict__ d_o, int64_t do_bstride, int64_t do_hs, int64_t do_ld,
+                                                                const float* __restrict__ lse, float* __restrict__ dvmean, int heads, int nq,
+                                                                float inv_nk, int n_prep, const int32_t* __restrict__ row_slot,
+                                                                float* __restrict__ rowc, int n_qtiles) {
+  if ((int)blockIdx.x >= n_prep) {
+    attn_dvmean_block((int)blockIdx.x - n_prep, (int)blockIdx.y, d_o, do_bstride, do_ld, lse, dvmean, heads, nq, inv_nk, do_hs);
+    return;
+  }
+  __shared__ float del_s[8][PREP_ROWS];
+  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int cols = heads * DH;
+  const int q_begin = (int)blockIdx.x * PREP_ROWS;
+  int q_end = q_begin + PREP_ROWS; if (q_end > nq) q_end = nq;
+  for (int c0 = 0; c0 < cols; c0 += 512) {
+    const int h0 = c0 / DH;
+    const int c = c0 + lane * 8;
+    const int hl = lane >> 3;
+    const int hh_ = c < cols ? h0 + hl : 0;          // (a lane past the last head re-reads head 0 and adds nothing)
+    bf16x8 ovs[PREP_ROWS / 4], dvs[PREP_ROWS / 4];
+#pragma unroll
+    for (int k = 0; k < PREP_ROWS / 4; k++) {
+      int q = q_begin + wave + 4 * k; if (q > nq - 1) q = nq - 1;
+      const int cc = c < cols ? c : 0;
+      ovs[k] = *reinterpret_cast<const bf16x8*>(o + (int64_t)b * o_bstride + (int64_t)q * o_ld + cc);
+      dvs[k] = *reinterpret_cast<const bf16x8*>(d_o + (int64_t)b * do_bstride + (int64_t)hh_ * do_hs + (int64_t)q * do_ld + (c < cols ? (lane & 7) * 8 : 0));
+    }
+#pragma unroll
+    for (int k = 0; k < PREP_ROWS / 4; k++) {
+      const int q = q_begin + wave + 4 * k;
+      if (q >= q_end) break;
+      float part = 0.f;
+      if (c < cols) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) part += bf2f((u16)dvs[k][j]) * bf2f((u16)ovs[k][j]);
+      }
+      part += __shfl_xor(part, 1, WAVE); part += __shfl_xor(part, 2, WAVE); part += __shfl_xor(part, 4, WAVE);
+      if ((lane & 7) == 0) del_s[hl][q - q_begin] = part;
+    }
+    __syncthreads();
+    {
+      const int hh = tid / PREP_ROWS, r = tid % PREP_ROWS;
+      if (h0 + hh < heads && q_begin + r < q_end) {
+        const int q = q_begin + r, slot = row_slot[q];
+        float* dst = rowc + (((int64_t)b * heads + h0 + hh) * (n_qtiles + 1) + (slot >> 6)) * 128 + (slot & 63);          // (+ 1: the null tile)
+        dst[0] = -lse[((int64_t)b * heads + h0 + hh) * nq + q];
+        dst[64] = -del_s[hh][r];
+      }
+    }
+    __syncthreads();
+  }
+}
+extern "C" int mca_attn_bwd_prep_onepass_hm(const uint16_t* o, int64_t o_bstride, int64_t o_ld, const uint16_t* d_o, int64_t do_bstride,
+                                            int64_t do_hstride, int64_t do_ld, const float* lse, const int32_t* row_slot, float* rowc,
+                                            float* dvmean, int batch, int heads, int n, int n_qtiles, mca_stream_t stream) {
+  if (!o || !d_o || !lse || !row_slot || !rowc || !dvmean || batch <= 0 || heads <= 0 || n <= 0 || n_qtiles <= 0) return MCA_E_BADARG;
+  if (o_ld % 8 || o_bstride % 8 || do_ld % 8 || do_bstride % 8 || do_hstride % 8 || do_hstride < 0 || (uintptr_t)o % 16 || (uintptr_t)d_o % 16) return MCA_E_ALIGN;
+  if (heads > 65535 || batch > 65535) return MCA_E_UNSUPPORTED;
+  const int n_prep = (n + PREP_ROWS - 1) / PREP_ROWS;
+  hipLaunchKernelGGL(attn_bwd_prep_hm_kernel, dim3(n_prep + heads, batch), dim3(256), 0, as_stream(stream), o, o_bstride, o_ld, d_o, do_bstride,
+                     do_hstride ? do_hstride : (int64_t)DH, do_ld, lse, dvmean, heads, n, 1.f / (float)n, n_prep, row_slot, rowc, n_qtiles);
   return launch_status();
 }

@@ -687,7 +687,10 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(
 // rows + the 128 "gate" rows of the same columns (wave column wn = 0 holds a, wn = 1 gate), C = h [M, 2*N], G = g [M, N].
 // SAVED (with GEGLU): C = s = [gelu(gate) | a * gelu'(gate)], the backward's factors, in h's place (mca_gemm_nt_geglu_fwd_saved):
 // the 16 own-block stores of a tile are not made and the partner phase stores s_lo, s_hi and g: 24 stores as before.
-template <bool GEGLU, bool SAVED = false>
+// CB (plain form only, mca_gemm_nt_cb): C is stored column-blocked, [N / 64][M][64] with `ldc` = cbs elements between the 64-column
+// slabs: column n of row m at C + (n / 64) * cbs + m * 64 + n % 64.  Only the address of the 16 stores moves: a lane's 16 bytes stay
+// inside one slab row and eight lanes fill its 128 bytes; NST and every wait count are those of the row-major store.
+template <bool GEGLU, bool SAVED = false, bool CB = false>
 __global__ __launch_bounds__(512) void gemm_nt_persist256_kernel(
     const u16* __restrict__ A, int64_t lda, const u16* __restrict__ B, int64_t ldb, u16* __restrict__ C, int64_t ldc,
     u16* __restrict__ G, int64_t ldg, int M, int N, int K, int tiles_n, int nwg, int dbg) {
@@ -824,7 +827,9 @@ __global__ __launch_bounds__(512) void gemm_nt_persist256_kernel(
 #pragma unroll
       for (int u = 0; u < (SAVED ? 0 : 8); u++) {
         const int m = mw + i * 32 + (lane >> 4) + 4 * u;
-        u16* cp = C + (int64_t)m * ldc + nw + 8 * (lane & 15);
+        u16* cp;
+        if constexpr (CB) cp = C + (int64_t)((nw >> 6) + ((lane & 15) >> 3)) * ldc + (int64_t)m * 64 + 8 * (lane & 7);
+        else cp = C + (int64_t)m * ldc + nw + 8 * (lane & 15);
         if (m < M) PS_GSTORE(cp, o[u]);
       }
       if (GEGLU) {
@@ -1446,10 +1451,10 @@ static int launch_persist(const mca_gemm_plan& p, const gemm_operands& o, mca_st
   return launch_kernel<gemm_nt_persist_kernel<MODE, BIAS>>(p, s, o.A, o.lda, o.B, o.ldb, o.C, o.ldc, o.bias, o.residual, o.ldres, o.M, p.n, o.K,
                                                            p.tiles_n, p.nwg, p.dbg);
 }
-template <bool GEGLU, bool SAVED = false>
+template <bool GEGLU, bool SAVED = false, bool CB = false>          // CB: o.ldc is the slab stride cbs
 static int launch_persist256(const mca_gemm_plan& p, const gemm_operands& o, mca_stream_t s) {
   u16* g = GEGLU ? reinterpret_cast<u16*>(const_cast<float*>(o.residual)) : nullptr;
-  return launch_kernel<gemm_nt_persist256_kernel<GEGLU, SAVED>>(p, s, o.A, o.lda, o.B, o.ldb, reinterpret_cast<u16*>(o.C), o.ldc, g,
+  return launch_kernel<gemm_nt_persist256_kernel<GEGLU, SAVED, CB>>(p, s, o.A, o.lda, o.B, o.ldb, reinterpret_cast<u16*>(o.C), o.ldc, g,
                                                          GEGLU ? o.ldres : (int64_t)0, o.M, p.n, o.K, p.tiles_n, p.nwg, p.dbg);
 }
 template <auto KERNEL>
@@ -1490,6 +1495,7 @@ static int launch(const mca_gemm_plan& p, const gemm_operands& o, mca_stream_t s
     case MCA_GK_NT_PERSIST_GEGLU_BWD_SAVED: return launch_persist<5, false>(p, o, s);
     case MCA_GK_NT_PERSIST_GEGLU_FWD_SAVED: return launch_persist<6, false>(p, o, s);
     case MCA_GK_NT_PERSIST256_GEGLU_FWD_SAVED: return launch_persist256<true, true>(p, o, s);
+    case MCA_GK_NT_PERSIST256_CB: return launch_persist256<false, false, true>(p, o, s);
     case MCA_GK_TN: return launch_tn<gemm_tn_kernel<false>>(p, o, s);
     case MCA_GK_TN_256: return launch_tn<gemm_tn_256_kernel<false>>(p, o, s);
     case MCA_GK_TN_256X256: return launch_tn<gemm_tn_256x256_kernel<false>>(p, o, s);
@@ -1520,6 +1526,19 @@ extern "C" int mca_gemm_nt(const uint16_t* A, int64_t lda, const uint16_t* B, in
   const mca_nt_problem pr = {M, N, K, out_bf16, res_period, addr(C), addr(bias), addr(residual), ldc, ldres};
   const gemm_operands o = {A, lda, B, ldb, C, ldc, bias, residual, ldres, res_period, nullptr, nullptr, nullptr, (int)M, (int)K, nullptr};
   return launch(mca_plan_gemm_nt(pr, mca_knobs, num_cus()), o, stream);
+}
+
+// C = A·B^T (bf16) stored column-blocked, [N / 64][M][64] with cbs elements between the slabs (include/mca_hip.h)
+extern "C" int mca_gemm_nt_cb(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t cbs,
+                              int64_t M, int64_t N, int64_t K, mca_stream_t stream) {
+  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return MCA_E_BADARG;
+  if (K % 32 || lda % 8 || ldb % 8 || (uintptr_t)A % 16 || (uintptr_t)B % 16) return MCA_E_ALIGN;
+  if (lda < K || ldb < K) return MCA_E_BADARG;
+  if (M > (1LL << 30) || N > (1LL << 30)) return MCA_E_UNSUPPORTED;
+  mca_gemm_plan pl;
+  if (!mca_plan_gemm_nt_cb(M, N, K, addr(C), cbs, mca_knobs, num_cus(), &pl)) return MCA_E_UNSUPPORTED;
+  const gemm_operands o = {A, lda, B, ldb, C, cbs, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, (int)M, (int)K, nullptr};
+  return launch(pl, o, stream);
 }
 
 // C[M,N] (fp32) = A·B^T + LayerNorm(x) with the LayerNorm recomputed in the epilogue from x and its saved statistics.
@@ -1752,6 +1771,11 @@ extern "C" int mca_dbg_plan_gemm_nt(int entry, const mca_nt_problem* pr, int cus
       *out = mca_plan_gemm_nt_res_lnbwd(pr->M); return MCA_OK;
   }
   return MCA_E_BADARG;
+}
+extern "C" int mca_dbg_plan_gemm_nt_cb(int64_t M, int64_t N, int64_t K, uint64_t C, int64_t cbs, int cus, mca_gemm_plan* out) {
+  if (!out || M <= 0 || N <= 0 || K <= 0) return MCA_E_BADARG;
+  if (cus <= 0) cus = num_cus();
+  return mca_plan_gemm_nt_cb(M, N, K, C, cbs, mca_knobs, cus, out) ? MCA_OK : MCA_E_UNSUPPORTED;
 }
 extern "C" const char* mca_dbg_gemm_kernel_name(int kernel) { return mca_gemm_kernel_name(kernel); }
 extern "C" int mca_dbg_plan_gemm_tn(int64_t R, int64_t N, int64_t K, mca_gemm_plan* out) {

@@ -52,7 +52,9 @@ enum mca_gemm_kernel {
   MCA_GK_NT_PERSIST256_GEGLU_FWD_SAVED = MCA_GK_SAVED + MCA_GK_NT_PERSIST256_GEGLU_FWD,  // gemm_nt_persist256_kernel<true, true>
   // The full-row form (mca_gemm_nt_res_lnbwd): a workgroup owns whole rows of C and runs the LayerNorm backward's row body on
   // them.  Outside the counted table like the saved forms.
-  MCA_GK_NT_ROWS_LNBWD = 128                                                              // gemm_nt_rows_kernel
+  MCA_GK_NT_ROWS_LNBWD = 128,                                                             // gemm_nt_rows_kernel
+  // The column-blocked store (mca_gemm_nt_cb): the 256 x 256 bf16 kernel writing C as [N / 64][M][64].  Outside the counted table too.
+  MCA_GK_NT_PERSIST256_CB = 256                                                           // gemm_nt_persist256_kernel<false,false,true>
 };
 
 // the instantiation a value stands for, spelled as in gemm.hip without blanks
@@ -77,6 +79,7 @@ static inline const char* mca_gemm_kernel_name(int k) {
     case MCA_GK_NT_PERSIST_GEGLU_FWD_SAVED: return "gemm_nt_persist_kernel<6,false>";
     case MCA_GK_NT_PERSIST256_GEGLU_FWD_SAVED: return "gemm_nt_persist256_kernel<true,true>";
     case MCA_GK_NT_ROWS_LNBWD: return "gemm_nt_rows_kernel";
+    case MCA_GK_NT_PERSIST256_CB: return "gemm_nt_persist256_kernel<false,false,true>";
   }
   return k >= 0 && k < MCA_GK_COUNT ? names[k] : "?";
 }
@@ -152,6 +155,19 @@ static inline mca_gemm_plan mca_plan_gemm_nt(const mca_nt_problem& p, const int*
   }
   pl.grid_x = pl.nwg;
   return pl;
+}
+
+// C = A.B^T (bf16) stored COLUMN-BLOCKED (mca_gemm_nt_cb): column n of row m at C + (n / 64) * cbs + m * 64 + n % 64, cbs >= M * 64
+// elements between the 64-column slabs.  Only the 256 x 256 persistent kernel has the store, so the plan is mca_plan_gemm_nt's for a
+// packed bf16 C of the same shape - same grid, block, LDS bytes and knob word, knobs 1, 7 and 10 included - with the kernel value
+// swapped, wherever that plan is MCA_GK_NT_PERSIST256 and cbs keeps a lane's 16 bytes aligned.  false: refused (MCA_E_UNSUPPORTED).
+static inline bool mca_plan_gemm_nt_cb(int64_t M, int64_t N, int64_t K, uint64_t C, int64_t cbs, const int* knobs, int cus, mca_gemm_plan* out) {
+  const mca_nt_problem pr = {M, N, K, 1, 0, C, 0, 0, N, 0};
+  mca_gemm_plan pl = mca_plan_gemm_nt(pr, knobs, cus);
+  if (pl.kernel != MCA_GK_NT_PERSIST256 || cbs % 8 != 0 || cbs < M * 64) return false;
+  pl.kernel = MCA_GK_NT_PERSIST256_CB;
+  *out = pl;
+  return true;
 }
 
 // C = A.B^T + LayerNorm(x): the fused form exists for the large-M residual-prefetch kernel only (mca_gemm_nt_lnres refuses

@@ -53,10 +53,12 @@ def debug_options() -> dict:
     the weight-gradient, LayerNorm-backward, row-reduction and table-gradient launches: FusionEngine.set_deterministic),
     geglu_saved=0 (the FF1 GEMM keeps h = [a | gate] and the backward evaluates gelu again, instead of the saved factors:
     FusionEngine.geglu_saved_factors), ln_rows=0 (the trunk LayerNorm backward as a launch of its own behind the data-gradient
-    GEMM instead of in that GEMM's full-row epilogue: FusionEngine.fuse_ln_rows).  Kernel-level knobs: include/mca_hip_debug.h
-    (hip.knobs)."""
+    GEMM instead of in that GEMM's full-row epilogue: FusionEngine.fuse_ln_rows), qkv_hm=0 (q | k | v and dO always as row-major
+    matrices, with the one-pass backward's packed copies, instead of head-major from their GEMMs: FusionEngine.qkv_head_major).
+    Kernel-level knobs: include/mca_hip_debug.h (hip.knobs)."""
     opts = {"overlap_wgrad": None, "group_wgrad": True, "mask_mfma": True, "dkv_keys": 128, "lazy_softmax": True,
-            "onepass": None, "deterministic": False, "geglu_saved": True, "ln_rows": True}          # onepass=0|1: the one-pass attention backward (attention_bwd1.hip); default: by size
+            "onepass": None, "deterministic": False, "geglu_saved": True, "ln_rows": True,
+            "qkv_hm": True}          # onepass=0|1: the one-pass attention backward (attention_bwd1.hip); default: by size
     for item in filter(None, os.environ.get("MCA_DEBUG", "").split(",")):
         k, _, v = item.partition("=")
         k = k.strip()
@@ -131,6 +133,10 @@ class FusionEngine:
         # The trunk LayerNorm backward inside the data-gradient GEMM that produces its dy (mca_gemm_nt_res_lnbwd: a workgroup owns
         # whole rows, dy never reaches memory).  Where it applies: ln_rows_backward.
         self.fuse_ln_rows = bool(self.dbg["ln_rows"])
+        # q | k | v and dO written head-major by their GEMMs (mca_gemm_nt_cb) and read in place by the attention kernels, where the
+        # one-pass backward runs: qkv_head_major decides once per forward.  rows_only: a forward whose q | k are read afterwards
+        # by code that takes row-major matrices only (the attention readout) keeps the row-major layout.
+        self.rows_only = False
         # Weight-gradient GEMMs on a side stream, concurrent with the backward chain: None = by size (on below OVERLAP_ROWS_MAX
         # token rows).  Since the attention backward lost its atomics the main stream keeps every CU busy and the persistent
         # weight-gradient GEMMs of a second stream only take CUs from it (one box, alternating processes: 23.7 / 25.6 ms per
@@ -453,7 +459,8 @@ class FusionEngine:
                              # backward operands of the weight-gradient GEMMs: one set PER LAYER, so those GEMMs can run
                              # on a side stream without write-after-read hazards against the next layer's backward
                              dxo_b=bf(T, D), dx1_b=bf(T, D), dh=bf(T, 2 * Ip), dqkv=bf(T, 3 * D),
-                             h_holds=None)          # "h" = [a | gate] or "s" = the saved GEGLU factors: set by forward_trunk
+                             h_holds=None,          # "h" = [a | gate] or "s" = the saved GEGLU factors: set by forward_trunk
+                             qkv_hm=False)          # qkv holds [3 H][T][64] (mca_gemm_nt_cb) instead of (T, 3 D): set by forward_trunk
                         for _ in range(self.L)]
         ws["xn"], ws["x1n"] = f32(T, D), f32(T, D)
         ws["mf"], ws["rf"] = f32(T), f32(T)
@@ -471,7 +478,11 @@ class FusionEngine:
         ws["dropped"] = torch.zeros(b, dtype=torch.int32, device=dev)          # the modality dropout's drop bits (set_modality_dropout)
         # backward
         ws["dxa"], ws["dxb"], ws["dx_b"] = f32(T, D), f32(T, D), bf(T, D)
-        ws["dg"], ws["do"] = bf(T, Ip), bf(T, D)
+        ws["dg"] = bf(T, Ip)
+        # dO = dx1 Wo: (T, D), or [H][T][64] where the layer's q | k | v are head-major (ws["do_hm"] says which it holds).  64 rows of
+        # zeros behind it: the one-pass kernel reads whole 64-row tiles, the last head's last one past its rows
+        ws["do_buf"] = torch.zeros(T * D + 64 * 64, dtype=torch.bfloat16, device=dev)
+        ws["do"], ws["do_hm"] = ws["do_buf"][:T * D].view(T, D), False
         ws["dpool_b"], ws["dop"], ws["dqp32"], ws["dqp_sum"], ws["dqp_b"] = bf(b * R, D), bf(b * R, D), f32(b * R, D), f32(R, D), bf(R, D)
         ws["dkvp"], ws["drt"] = (None if self.eao else bf(T, 2 * D)), f32(R, D)
         sc = self.sched_onepass
@@ -480,10 +491,7 @@ class FusionEngine:
             rc[:, :, :, 0] = float("-inf"); rc[:, :, :, 1] = 0.0          # positions past a tile's rows: -inf | 0 (written once; the prep kernel only touches real rows)
             ws["rowc"] = rc
             ws["dq_acc"] = f32(b * H * self.backward_plan(ws, b, N).split * (sc.n_qt + 1) * 4096)          # (+ the null tile's slot)
-            # head-major packed copies of q and dO (written by the prep launch): a query tile of a head is contiguous memory
-            # (+ 64 rows: the kernel reads whole 64-row tiles, the last one past its rows)
-            ws["q_hm"] = torch.zeros((b * H * N + 64) * 64, dtype=torch.bfloat16, device=dev)
-            ws["do_hm"] = torch.zeros((b * H * N + 64) * 64, dtype=torch.bfloat16, device=dev)
+            # (the head-major packed copies of q and dO, for a backward on row-major operands: _packed_copies, on first use)
         ws["enc"] = {s.name: s.workspace(b, f32, bf, u8) for s in self.enc_steps}
         ws["side"], ws["side_events"] = torch.cuda.Stream(device=dev), []          # side stream of the weight-gradient GEMMs
         if self._deterministic:
@@ -591,13 +599,62 @@ class FusionEngine:
         go through _ln_bwd"""
         call("mca_layernorm_bwd", *_ln_bwd_args(*args, **optional), stream_ptr())
 
+    def qkv_head_major(self, ws) -> bool:
+        """Whether this forward's QKV GEMMs write q | k | v head-major ([3 H][T][64], mca_gemm_nt_cb) for the attention kernels to read
+        in place - and the backward's dx1 Wo GEMM dO likewise - instead of the (T, 3 D) matrix: where the layer attention's
+        backward is the one-pass kernel (its prep launch then copies nothing), on bf16 operands, for GEMM shapes the column-blocked
+        store exists for under the current knobs, and unless the forward is read out afterwards (rows_only) or MCA_DEBUG=qkv_hm=0.
+        Decided once per forward; what a layer's buffer holds is recorded as a["qkv_hm"]."""
+        if not self.dbg["qkv_hm"] or self.rows_only or self.attn_dtype != "bf16" or ws.get("present_cur") is None:
+            return False          # (present_cur: mean(V) has its head-major form in the presence-bit entry point only)
+        T, D = ws["T"], self.D
+        if self.backward_plan(ws, ws["b"], self.N).form != "onepass":
+            return False
+        pl = hip.GemmPlan()
+        return all(hip.lib().mca_dbg_plan_gemm_nt_cb(T, n, D, 0, T * 64, 1, C.byref(pl)) == 0 for n in (3 * D, D))
+
+    @staticmethod
+    def gemm_nt_cb(A, B, Cbuf, M, N, K):
+        """C = A B^T (bf16) as [N / 64][M][64] (mca_gemm_nt_cb), timed in the row of the mca_gemm_nt launch it replaces"""
+        if hip.PROFILE is not None:
+            hip.set_tag(f"{M}x{N}x{K}")
+        call("mca_gemm_nt_cb", ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(Cbuf), M * 64, M, N, K, stream_ptr(), flops=2.0 * M * N * K,
+             profile_as="mca_gemm_nt")
+        if hip.PROFILE is not None:
+            hip.set_tag("")
+
+    def _packed_copies(self, ws):
+        """q_hm, do_hm: the packed copies mca_attn_bwd_prep_onepass writes for a one-pass backward on ROW-MAJOR q and dO (+ 64 rows:
+        the kernel reads whole 64-row tiles, the last one past its rows).  Allocated on first use: a step that keeps q | k | v and
+        dO head-major never needs them."""
+        if "q_hm" not in ws:
+            n = (ws["b"] * self.H * self.N + 64) * 64
+            ws["q_hm"], ws["do_hm_copy"] = (torch.zeros(n, dtype=torch.bfloat16, device=self.device) for _ in range(2))
+        return ws["q_hm"], ws["do_hm_copy"]
+
+    def _to_row_major(self, ws, i):
+        """Layer i's q | k | v and dO back into their row-major matrices, in place.  Only where the backward form changed between a
+        head-major forward and the backward (MCA_DEBUG / engine.dbg switched in between, as the A/B tests do): never in a step."""
+        a, T, H = ws["layers"][i], ws["T"], self.H
+        if a["qkv_hm"]:
+            a["qkv"].copy_(a["qkv"].view(3 * H, T, 64).permute(1, 0, 2).reshape(T, 3 * H * 64))
+            a["qkv_hm"] = False
+        if ws["do_hm"]:
+            ws["do"].copy_(ws["do"].view(H, T, 64).permute(1, 0, 2).reshape(T, H * 64))
+            ws["do_hm"] = False
+
     def layer_attention(self, ws, i):
         """-> (AttnOperands, AttnGrads) of fusion layer i: q | k | v and dq | dk | dv are the column blocks of the packed (T, 3D)
-        qkv / dqkv matrices"""
-        D, N, a = self.D, self.N, ws["layers"][i]
-        return (AttnOperands(a["qkv"].data_ptr(), N * 3 * D, 3 * D, a["qkv"], D, 2 * D, 3 * D, a["o"], a["lse"], N, self.qmask_attn,
-                             self.qblk_attn, self.sched_attn_f, self.sched_attn_b2, i),
-                AttnGrads(ws["do"], ws["delta"], a["dqkv"].data_ptr(), N * 3 * D, 3 * D, False, a["dqkv"], D, 2 * D, 3 * D))
+        qkv / dqkv matrices; q | k | v (a["qkv_hm"]) and dO (ws["do_hm"]) head-major where their GEMMs wrote them so"""
+        D, N, H, T, a = self.D, self.N, self.H, ws["T"], ws["layers"][i]
+        if a["qkv_hm"]:          # [3 H][T][64]: q, k, v are slabs 0, H, 2 H; a (sample, head) is N contiguous 64-element rows
+            ops = AttnOperands(a["qkv"].data_ptr(), N * 64, 64, a["qkv"], H * T * 64, 2 * H * T * 64, 64, a["o"], a["lse"], N, self.qmask_attn,
+                               self.qblk_attn, self.sched_attn_f, self.sched_attn_b2, i, T * 64)
+        else:
+            ops = AttnOperands(a["qkv"].data_ptr(), N * 3 * D, 3 * D, a["qkv"], D, 2 * D, 3 * D, a["o"], a["lse"], N, self.qmask_attn,
+                               self.qblk_attn, self.sched_attn_f, self.sched_attn_b2, i)
+        return ops, AttnGrads(ws["do"], ws["delta"], a["dqkv"].data_ptr(), N * 3 * D, 3 * D, False, a["dqkv"], D, 2 * D, 3 * D,
+                              T * 64 if ws["do_hm"] else 0)
 
     def pool_attention(self, ws):
         """-> (AttnOperands, AttnGrads) of the attentive pooling: one (R, D) q for every sample, k | v packed as (T, 2D), dq fp32"""
@@ -614,7 +671,11 @@ class FusionEngine:
         N, b = self.N, ws["b"]
         a = attention.fwd_args(ops, self.attn_keys(ws), ws["vmean"])
         # mean(V) is the output of fully masked rows only: samples with every modality present have none and are skipped
-        if ws.get("present_cur") is not None:
+        if ops.hstride:
+            assert ws.get("present_cur") is not None and self.attn_dtype == "bf16", "head-major q | k | v: the engine's own bf16 forward only"
+            call("mca_attn_vmean_if_needed_hm", a.v, a.kv_bstride, a.kv_ld, ops.hstride, ws["vmean"].data_ptr(), b, N, self.H,
+                 ptr(ws["present_cur"]), (1 << self.M) - 1, stream_ptr(), profile_as="mca_attn_vmean_if_needed")
+        elif ws.get("present_cur") is not None:
             call("mca_attn_vmean_if_needed", a.v, a.kv_bstride, a.kv_ld, ws["vmean"].data_ptr(), b, N, self.H, ptr(ws["present_cur"]),
                  (1 << self.M) - 1, stream_ptr())
         else:
@@ -630,10 +691,22 @@ class FusionEngine:
         (sample, head) takes the one-pass form."""
         b, keys = ws["b"], self.attn_keys(ws)
         plan = self.backward_plan(ws, b, ops.nq, grads.dq_f32)
+        if ops.hstride or grads.do_hstride:
+            # head-major operands are the one-pass kernel's alone, q | k | v and dO together.  Anything else - the plan changed since
+            # the forward, or these records are older than such a change - goes back to the row-major matrices first
+            a = ws["layers"][ops.layer]
+            if plan.form != "onepass" or not (a["qkv_hm"] and ws["do_hm"]):
+                self._to_row_major(ws, ops.layer)
+                ops, grads = self.layer_attention(ws, ops.layer)
         if plan.form == "onepass":
             sc = self.sched_onepass
             assert ws["dq_acc"].numel() >= b * self.H * plan.split * (sc.n_qt + 1) * 4096, "dq_acc of this workspace is too small for the split"
-            attention.backward_onepass(ops, grads, keys, sc, ws["rowc"], ws["dq_acc"], ws["dvmean"], ws["q_hm"], ws["do_hm"], plan.split)
+            if ops.hstride:
+                assert ops.hstride == grads.do_hstride == ws["T"] * 64 and ws["layers"][ops.layer]["qkv_hm"] and ws["do_hm"], \
+                    f"layer {ops.layer}: q | k | v and dO are not both head-major as the forward recorded"
+                attention.backward_onepass_hm(ops, grads, keys, sc, ws["rowc"], ws["dq_acc"], ws["dvmean"], plan.split)
+            else:
+                attention.backward_onepass(ops, grads, keys, sc, ws["rowc"], ws["dq_acc"], ws["dvmean"], *self._packed_copies(ws), plan.split)
         elif plan.form == "fp8-twopass":
             attention.backward_twopass(ops, grads, keys, ws["dvmean"], *self._fp8_bwd_operands(ws, b, ops.layer))
         else:
@@ -751,12 +824,14 @@ class FusionEngine:
         ln_in_gemm = self.ln_in_gemm(T)
         saved = self.geglu_saved_factors and self.fuse_geglu_bwd
         ff1 = "mca_gemm_nt_geglu_fwd_saved" if saved else "mca_gemm_nt_geglu_fwd"
+        qkv_hm = self.qkv_head_major(ws)
         for i, ly in enumerate(m.layers):
             w, a = self.wl[i], ws["layers"][i]
             xin, xout = ws["x"][i], ws["x"][i + 1]
             g = ly.norm.gamma
             self.ln_fwd(xin, g, T, D, a["m1"], a["r1"], y=None if ln_in_gemm else ws["xn"], ldy=D, y_bf16=a["xn_b"], cols_pad=D)
-            self.gemm_nt(a["xn_b"], w["qkv"], a["qkv"], T, 3 * D, D)
+            a["qkv_hm"] = qkv_hm
+            (self.gemm_nt_cb if qkv_hm else self.gemm_nt)(a["xn_b"], w["qkv"], a["qkv"], T, 3 * D, D)
             self.attn_forward(self.layer_attention(ws, i)[0], ws)
             if ln_in_gemm:
                 call("mca_gemm_nt_lnres", ptr(a["o"]), D, ptr(w["o"]), D, ptr(a["x1"]), D, ptr(xin), D, ptr(a["m1"]), ptr(a["r1"]),
@@ -1029,7 +1104,9 @@ class FusionEngine:
             # x1 = o @ Wo^T + xn
             if not grouped:
                 on_side(lambda dx1=dx1, a=a, ly=ly: tn(dx1, a["o"], G(ly.attn.to_out.weight), T, D, D))
-            self.gemm_nt(dx1, w["oT"], ws["do"], T, D, D)
+            # dO head-major beside a head-major q | k | v (the one-pass backward reads both in place)
+            ws["do_hm"] = a["qkv_hm"] and self.backward_plan(ws, b, self.N).form == "onepass"
+            (self.gemm_nt_cb if ws["do_hm"] else self.gemm_nt)(dx1, w["oT"], ws["do"], T, D, D)
             # dq | dk | dv land in dqkv as bf16, each element written once
             self.attn_backward(*self.layer_attention(ws, i), ws)
             # to_q.weight and to_kv.weight are adjacent in the flat gradient buffer: one (3D, D) weight-gradient GEMM

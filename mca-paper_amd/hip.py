@@ -134,6 +134,11 @@ class AttnBwd1Args(C.Structure):
     ]
 
 
+class AttnLayout(C.Structure):
+    """mca_attn_layout: elements between the heads of q and of k | v where they are not the 64-column blocks of a row (0 = 64)"""
+    _fields_ = [("q_hstride", C.c_int64), ("kv_hstride", C.c_int64)]
+
+
 # the GEMM planners' structs (csrc/gemm_plan.h; filled by the mca_dbg_plan_gemm_* hooks)
 class GemmPlan(C.Structure):
     _fields_ = [(f, C.c_int) for f in ("kernel", "grid_x", "grid_y", "block", "lds_bytes", "n", "tiles_n", "nwg", "tiles_k",
@@ -165,6 +170,7 @@ PLAN_NT, PLAN_LNRES, PLAN_GEGLU_FWD, PLAN_GEGLU_BWD, PLAN_GEGLU_FWD_SAVED, PLAN_
 GK_SAVED = 64          # csrc/gemm_plan.h MCA_GK_SAVED: a saved-factor kernel's value is its unsaved sibling's + this
 PLAN_RES_LNBWD = 6     # mca_gemm_nt_res_lnbwd
 GK_NT_ROWS_LNBWD = 128          # csrc/gemm_plan.h MCA_GK_NT_ROWS_LNBWD: gemm_nt_rows_kernel
+GK_NT_PERSIST256_CB = 256       # csrc/gemm_plan.h MCA_GK_NT_PERSIST256_CB: the 256 x 256 kernel with the column-blocked store (mca_gemm_nt_cb)
 
 
 # the LayerNorm planners' structs (csrc/ln_plan.h; filled by mca_dbg_plan_layernorm_fwd / _bwd).  Pointers travel as integers.
@@ -202,6 +208,7 @@ SIGNATURES = {
     "mca_segment_mean_fwd": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
     "mca_segment_mean_bwd": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "mca_gemm_nt": (_I, [_P, _I64, _P, _I64, _P, _I64, _I, _P, _P, _I64, _I64, _I64, _I64, _I64, _P]),
+    "mca_gemm_nt_cb": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),          # A, lda, B, ldb, C, cbs, M, N, K
     "mca_gemm_nt_geglu_bwd": (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P]),
     "mca_gemm_nt_lnres": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _P]),
     "mca_gemm_nt_geglu_fwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
@@ -237,6 +244,12 @@ SIGNATURES = {
     "mca_attn_vmean": (_I, [_P, _I64, _I64, _P, _I, _I, _I, _P]),
     "mca_attn_vmean_if_needed": (_I, [_P, _I64, _I64, _P, _I, _I, _I, _P, _I, _P]),
     "mca_attn_fwd": (_I, [C.POINTER(AttnFwdArgs), _P]),
+    # the _hm forms: head strides beside the unchanged structs (AttnLayout)
+    "mca_attn_fwd_hm": (_I, [C.POINTER(AttnFwdArgs), C.POINTER(AttnLayout), _P]),
+    "mca_attn_vmean_if_needed_hm": (_I, [_P, _I64, _I64, _I64, _P, _I, _I, _I, _P, _I, _P]),
+    "mca_attn_bwd_onepass_hm": (_I, [C.POINTER(AttnBwd1Args), C.POINTER(AttnLayout), _P]),
+    # o, o_bstride, o_ld, d_o, do_bstride, do_hstride, do_ld, lse, row_slot, rowc, dvmean, batch, heads, n, n_qtiles
+    "mca_attn_bwd_prep_onepass_hm": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "mca_attn_readout": (_I, [C.POINTER(AttnReadoutArgs), _P]),
     "mca_attn_quant_mxfp8": (_I, [_P, _I64, _I64, _P, _P, _I64, _I64, C.POINTER(AttnFp8Operands), _I, _I, _I, _P]),
     "mca_attn_fwd_fp8": (_I, [C.POINTER(AttnFwdArgs), C.POINTER(AttnFp8Operands), _P]),
@@ -288,6 +301,7 @@ DEBUG_SIGNATURES = {
     "mca_debug_reset": (_I, []),
     "mca_dbg_gemm_kernel_name": (C.c_char_p, [_I]),
     "mca_dbg_plan_gemm_nt": (_I, [_I, C.POINTER(NtProblem), _I, C.POINTER(GemmPlan)]),
+    "mca_dbg_plan_gemm_nt_cb": (_I, [_I64, _I64, _I64, C.c_uint64, _I64, _I, C.POINTER(GemmPlan)]),          # M, N, K, C, cbs, cus
     "mca_dbg_plan_gemm_tn": (_I, [_I64, _I64, _I64, C.POINTER(GemmPlan)]),
     "mca_dbg_plan_gemm_tn_group": (_I, [C.POINTER(_I64), C.POINTER(_I64), _I, _I64, _I, C.POINTER(TnGroupPlan)]),
     "mca_dbg_plan_gemm_tn_det": (_I, [_I64, _I64, _I64, C.POINTER(TnDetPlan)]),

@@ -44,6 +44,8 @@ def slot_mass(pool_mass: torch.Tensor, slots: Dict[object, int]) -> Dict[object,
 
 def launch(engine, ops, ws, mass: torch.Tensor, um: torch.Tensor, probs: Optional[torch.Tensor] = None, row0: int = 0):
     """one mca_attn_readout launch on the operands of an attention whose forward has run (ops: attention.AttnOperands)"""
+    if ops.hstride:
+        raise hip.MCAHipError("mca_attn_readout reads row-major q | k: run the forward with engine.rows_only set (attention_readout does)")
     a = attention.readout_args(ops, engine.attn_keys(ws), um, mass, probs, row0)
     hip.call("mca_attn_readout", C.byref(a), hip.stream_ptr())
 
@@ -68,8 +70,13 @@ def attention_readout(model, batch, layers: Optional[Iterable[int]] = None, pool
             raise KeyError(f"probs_rows[{key!r}]: not among the requested attentions")
         if row0 < 0 or n <= 0 or row0 + n > nq:
             raise IndexError(f"probs_rows[{key!r}] = ({row0}, {n}) outside [0, {nq})")
-    with torch.no_grad():
-        out = model(batch, no_loss=True)
+    # (mca_attn_readout takes q | k as row-major matrices: this forward keeps them so at every batch size)
+    rows_only, eng.rows_only = eng.rows_only, True
+    try:
+        with torch.no_grad():
+            out = model(batch, no_loss=True)
+    finally:
+        eng.rows_only = rows_only
     b = next(iter(out["modality_sample_mask"].values())).shape[0]
     ws = eng.workspace(b)
     dev, H, N, R = eng.device, eng.H, eng.N, eng.R
