@@ -640,6 +640,49 @@ int mca_probe_tn_f32(const float* a, int64_t lda, const float* b, int64_t ldb, c
 /* acc[0] += (sum of n loss partials, fixed order) / count */
 int mca_probe_loss_accum(const float* loss_part, int64_t n, int64_t count, float* acc, mca_stream_t stream);
 
+/* ---- Supervised task head over the pooled tokens (fine-tuning; finetune.py).  A linear head nn.Linear(D, L) reads ONE slot of the
+ * (b, R, D) pooled tokens, x[s, :] = pooled[s, slot, :] (signed values: no activation gate), and an elementwise loss compares its
+ * logits with a column window of a label matrix.  Row s is VALID iff any_bits == 0 or (present[s] & any_bits) != 0; n_valid counts
+ * the valid rows and n = n_valid * L.
+ *   pred[s, l]   = z[s, l] = x[s] . w[l] + bias[l], written for every row, valid or not
+ *   loss[0]      = mean element loss over the n elements of the valid rows, NOT scaled by task_weight (0 when n_valid == 0);
+ *   loss[1]      = n_valid.  Element loss by loss_type: 0 |z - y|, 1 (z - y)^2, 2 max(z, 0) - z y + log1p(exp(-|z|))
+ *   dz[s, l]     = (d element loss / dz) * fl(task_weight / n) on valid rows (sign(0) = 0 for L1), 0 on invalid rows and when
+ *                  n_valid == 0; the labels of an invalid row are never read
+ *   gw[l, k]     = sum_s dz[s, l] x[s, k], gb[l] = sum_s dz[s, l]   (accumulate 0: overwritten, 1: added to)
+ *   d_pooled[s, r, :] = base_weight * d_pooled_in[s, r, :] + (r == slot ? sum_l dz[s, l] w[l, :] : 0), one fused multiply-add per
+ *                  element, every element written; d_pooled_in NULL: base_weight is ignored and the base is 0.
+ * Two launches: one workgroup per 64 rows (one wave per row) stores its share of gw, gb and the loss into its slot of the
+ * workspace, rows in order; the second launch adds the slots in block order.  No atomics: two calls on unchanged inputs give the
+ * same bits.  Rows of pooled, w, d_pooled and gw move as 16-byte accesses.
+ * MCA_E_BADARG: args or a required pointer NULL, b < 1, R < 1, D < 1, L < 1, slot outside [0, R), ld_labels < L, loss_type outside
+ * 0 .. 2, accumulate not 0 / 1, present NULL with any_bits != 0, a NaN weight, workspace_bytes below the query.
+ * MCA_E_UNSUPPORTED: D > 1024 or L > 64.  MCA_E_ALIGN: D % 4 != 0; pooled, w, d_pooled, d_pooled_in, gw or workspace not 16-byte
+ * aligned; another pointer not 4-byte aligned.  Every check returns before anything is launched.                              */
+typedef struct {
+  const float* pooled;              /* (b, R, D) dense fp32                                          */
+  const uint32_t* present;          /* (b) presence words of the step, or NULL (any_bits == 0)       */
+  uint32_t any_bits;
+  int b, R, D, slot;
+  const float* w; const float* bias;          /* (L, D) row-major, (L)                               */
+  int L;
+  const float* labels;              /* y[s, l] = labels[s * ld_labels + l]                           */
+  int64_t ld_labels;
+  int loss_type;                    /* 0 L1, 1 MSE, 2 BCE with logits (mca_probe_head_f32's codes)   */
+  float task_weight, base_weight;
+  const float* d_pooled_in;         /* (b, R, D) or NULL                                             */
+  float* pred;                      /* (b, L)                                                        */
+  float* loss;                      /* [2]                                                           */
+  float* d_pooled;                  /* (b, R, D); may alias d_pooled_in                              */
+  float* gw; float* gb;             /* (L, D), (L)                                                   */
+  int accumulate;
+  float* workspace; int64_t workspace_bytes;
+} mca_task_head_args;
+/* bytes of workspace mca_task_head_fwd_bwd needs (host only): ceil(b / 64) slots of L*D + roundup4(L) + 4 floats; -1 for sizes the
+ * entry point refuses (b < 1, L outside 1 .. 64, D outside 4 .. 1024 or D % 4 != 0)                                              */
+int64_t mca_task_head_workspace_bytes(int b, int L, int D);
+int mca_task_head_fwd_bwd(const mca_task_head_args* args, mca_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Deterministic mode: fixed-order forms of the six entry points whose parameter gradients are sums of
  * fp32 atomics ("Deterministic mode").  Each takes the arguments of its plain form plus
