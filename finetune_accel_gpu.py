@@ -3,17 +3,20 @@ INTEGRATION.md section I):
 
     python finetune_accel_gpu.py <config.yaml> [--synthetic N]
 
-The config is the training YAML (train_accel_gpu.py) plus a ``finetune:`` mapping: loss_type (L1 | MSE | BCE, default MSE), task (a
+The config is the training YAML (train_accel_gpu.py) plus a ``finetune:`` mapping: loss_type (L1 | MSE | BCE | CE, default MSE), task (a
 column of ``label_col``, -1 = all columns; default 0), readout (a pooled slot: a modality name, "fusion" or a list of modality names for
 a combination; default fusion), head_lr (default: lr), task_weight (1.0), contrastive_weight (0.0), head_warmup_steps (0).  Unknown
-keys are an error.  ``restart`` names the pretrained checkpoint (model only; a ``head_state.pt`` beside it is loaded too, and the
+keys are an error.  loss_type CE (softmax cross-entropy; column ``task`` holds class indices, a negative one marks an unlabelled row)
+adds num_classes (2 .. 64, required), class_weights (a list of num_classes weights) and label_smoothing (0.0); they are an error with
+any other loss.  ``restart`` names the pretrained checkpoint (model only; a ``head_state.pt`` beside it is loaded too, and the
 restored pair is evaluated once before training, logged as epoch -1); empty: training starts from the seed, and the run says so.
 
 One linear head is trained with the trunk for ``epochs`` epochs, both learning rates on the configured schedule; after every epoch the
 eval split is predicted and ONE JSON record is printed and appended to <output_dir>/log.jsonl: epoch, train_loss, eval_loss,
-eval_PCC (per task column) or eval_<the probe's binary metrics>, lr, grad_norm.  At the end <output_dir> holds the state
+eval_PCC (per task column), eval_<the probe's binary metrics> or, for CE, eval_<the multiclass metrics> over the valid and labelled rows
+(eval_loss is then float64 cross_entropy with the same weights and smoothing, eval_cm a nested list), lr, grad_norm.  At the end <output_dir> holds the state
 (checkpoint.save_state) and head_state.pt.  --synthetic N: N random train and N random eval batches with randn (b, 7) labels
-(thresholded at 0 for BCE).  ``batch_dropout: true`` works as in training.  grad_cache_chunks > 1 and --graph are refused."""
+(thresholded at 0 for BCE; CE: column ``task`` drawn uniformly from 0 .. num_classes - 1).  ``batch_dropout: true`` works as in training.  grad_cache_chunks > 1 and --graph are refused."""
 import importlib
 import json
 import os
@@ -48,6 +51,17 @@ def evaluate(step, batches, label_col, device):
         y = y if step.task < 0 else y[:, step.task:step.task + 1]
         preds.append(pred[valid]); labels.append(y[valid])
     pred, y = torch.cat(preds), torch.cat(labels)
+    if step.loss_type == "CE":
+        y = y[:, 0]
+        keep = y >= 0          # the labelled rows
+        pred, y = pred[keep], y[keep].long()
+        cw = None if step.class_weights is None else step.class_weights.double()
+        rec = {"eval_loss": float(torch.nn.functional.cross_entropy(pred.double(), y, weight=cw, label_smoothing=step.label_smoothing))
+               if pred.numel() else None}
+        if pred.numel():
+            for k, v in P.metrics.multiclass_metrics(torch.softmax(pred.double(), 1), y).items():
+                rec[f"eval_{k}"] = v.tolist()
+        return rec
     rec = {"eval_loss": float(element_loss(pred, y, step.loss_type)) if pred.numel() else None}
     if step.loss_type == "BCE":
         for k, v in P.metrics.binary_metrics(torch.sigmoid(pred), y).items():
@@ -78,6 +92,9 @@ def main():
             for i in range(synthetic):
                 b = P.data.synthetic_batch(model_config, config.batch_size, seed=seed0 + i, p_drop=0.2)
                 y = torch.randn(config.batch_size, 7, generator=torch.Generator().manual_seed(seed0 + i))
+                if settings["loss_type"] == "CE":
+                    y[:, settings["task"]] = torch.randint(0, settings["num_classes"], (config.batch_size,),
+                                                           generator=torch.Generator().manual_seed(seed0 + i)).float()
                 b[label_col] = {"data": (y > 0).float() if settings["loss_type"] == "BCE" else y}
                 yield b
         train_batches, eval_batches = (lambda epoch: split(100 + 1000 * epoch)), (lambda: split(10_000))
@@ -99,7 +116,8 @@ def main():
     model = P.build_model(model_config).to(device)
     opt = optim.FusedAdamW(model, lr=config.lr)
     model.engine.check_finite = "deferred"
-    head = finetune.TaskHead(model_config["dim"], n_labels if settings["task"] < 0 else 1)
+    n_outputs = settings["num_classes"] if settings["loss_type"] == "CE" else (n_labels if settings["task"] < 0 else 1)
+    head = finetune.TaskHead(model_config["dim"], n_outputs)
     step = finetune.FineTuneStep(model, head, opt, clip=config.clip or 0.0, **settings)
     restored = False
     if config.restart:

@@ -683,6 +683,67 @@ typedef struct {
 int64_t mca_task_head_workspace_bytes(int b, int L, int D);
 int mca_task_head_fwd_bwd(const mca_task_head_args* args, mca_stream_t stream);
 
+/* ---- Softmax cross-entropy over class-index labels (csrc/class_head.hip): the classification twins of mca_probe_head_f32 and
+ * mca_task_head_fwd_bwd.  One wavefront per row, one class per lane (C <= 64); the row maximum m is subtracted before expf, S is the
+ * sum of the exponentials and the row's negative log-likelihood is (m + logf(S)) - z_y.  A label is a CLASS INDEX when it is an
+ * integer value in [0, C); anything else (negative, >= C, fractional, NaN) is none and never indexes anything.
+ *
+ * Probe head, plain nn.CrossEntropyLoss(): the operands of mca_probe_head_f32 with C classes for its L outputs and ONE label a row,
+ * y_r = labels[yidx[r] * ldy] (yidx may be NULL: row r), ldy >= 1.  pred[r, c] = z[r, c] = a[aidx[r]] . w[c] + bias[c];
+ * row loss = -log softmax(z_r)[y_r]; dz (may be NULL) [B, C] = (softmax(z_r) - onehot(y_r)) / B; da (may be NULL) [B, K] as
+ * mca_probe_head_f32 forms it from dz; loss_part[mca_probe_head_blocks(B)] = per-block sums of the row losses (the caller passes
+ * count = B to mca_probe_loss_accum).  A row whose label is no class index gets loss 0 and dz 0; the divisor stays B.
+ * MCA_E_BADARG: a required pointer NULL, B, K < 1, C < 2, lda < K, ldy < 1.  MCA_E_UNSUPPORTED: K > 1024 or C > 64.             */
+int mca_probe_head_ce_f32(const float* a, int64_t lda, const int32_t* aidx, int64_t K, const float* w, const float* bias, int64_t C,
+                          const float* labels, int64_t ldy, const int32_t* yidx, int64_t B, float* pred, float* dz, float* da,
+                          float dact_scale, float* loss_part, mca_stream_t stream);
+
+/* Class head over the pooled tokens (fine-tuning): mca_task_head_fwd_bwd with the softmax cross-entropy of C classes for its
+ * elementwise losses.  x[s, :] = pooled[s, slot, :]; y_s = labels[s * ld_labels].  Row s is COUNTED iff it is valid by presence
+ * (any_bits == 0 or (present[s] & any_bits) != 0) and y_s is a class index; a negative label marks an unlabelled row, and every
+ * other label that is no class index is treated the same way.  The label of a row that is invalid by presence is never read.
+ * With cw = class_weights (all ones when NULL), eps = label_smoothing, p_s = softmax(z_s) and W = sum of cw[y_s] over counted rows:
+ *   pred[s, c]   = z[s, c] = x[s] . w[c] + bias[c], written for every row
+ *   loss[0]      = (1 / W) sum_s [ (1 - eps) cw[y_s] (-log p_s[y_s]) + (eps / C) sum_c cw[c] (-log p_s[c]) ] over counted rows, NOT
+ *                  scaled by task_weight: torch's cross_entropy(z, y, weight=cw, label_smoothing=eps, reduction="mean") over the
+ *                  counted rows.  0 when W == 0 (nothing counted, or only classes of weight 0).
+ *   loss[1]      = the number of counted rows;  loss[2] = W
+ *   dz[s, c]     = fl(task_weight / W) * [ (1 - eps) cw[y_s] (p_s[c] - [c == y_s]) + (eps / C) (p_s[c] sum_k cw[k] - cw[c]) ] on
+ *                  counted rows, 0 elsewhere and when W == 0
+ *   gw, gb, d_pooled (base_weight, d_pooled_in, aliasing) and accumulate: exactly as in mca_task_head_fwd_bwd.
+ * Two launches: one workgroup per 64 rows (one wave per row) stores its share of gw, gb and the loss into its slot of the
+ * workspace, rows in order; the second launch adds the slots in block order.  Every workgroup forms the count and W itself, all by
+ * the same order.  No atomics: two calls on unchanged inputs give the same bits.  Rows of pooled, w, d_pooled and gw move as
+ * 16-byte accesses.
+ * MCA_E_BADARG: args or a required pointer NULL, b < 1, R < 1, D < 1, C < 2, slot outside [0, R), ld_labels < 1, label_smoothing
+ * outside [0, 1) or NaN, accumulate not 0 / 1, present NULL with any_bits != 0, a NaN weight, workspace_bytes below the query.
+ * MCA_E_UNSUPPORTED: D > 1024 or C > 64.  MCA_E_ALIGN: D % 4 != 0; pooled, w, d_pooled, d_pooled_in, gw or workspace not 16-byte
+ * aligned; another pointer not 4-byte aligned.  Every check returns before anything is launched.                              */
+typedef struct {
+  const float* pooled;              /* (b, R, D) dense fp32                                          */
+  const uint32_t* present;          /* (b) presence words of the step, or NULL (any_bits == 0)       */
+  uint32_t any_bits;
+  int b, R, D, slot;
+  const float* w; const float* bias;          /* (C, D) row-major, (C)                               */
+  int C;
+  const float* labels;              /* y_s = labels[s * ld_labels]: one fp32 class index a row       */
+  int64_t ld_labels;
+  const float* class_weights;       /* (C), or NULL for all ones                                     */
+  float label_smoothing;            /* in [0, 1)                                                     */
+  float task_weight, base_weight;
+  const float* d_pooled_in;         /* (b, R, D) or NULL                                             */
+  float* pred;                      /* (b, C) logits                                                 */
+  float* loss;                      /* [3]                                                           */
+  float* d_pooled;                  /* (b, R, D); may alias d_pooled_in                              */
+  float* gw; float* gb;             /* (C, D), (C)                                                   */
+  int accumulate;
+  float* workspace; int64_t workspace_bytes;
+} mca_class_head_args;
+/* bytes of workspace mca_class_head_fwd_bwd needs (host only): ceil(b / 64) slots of C*D + roundup4(C) + 4 floats; -1 for sizes the
+ * entry point refuses (b < 1, C outside 2 .. 64, D outside 4 .. 1024 or D % 4 != 0)                                             */
+int64_t mca_class_head_workspace_bytes(int b, int C, int D);
+int mca_class_head_fwd_bwd(const mca_class_head_args* args, mca_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Deterministic mode: fixed-order forms of the six entry points whose parameter gradients are sums of
  * fp32 atomics ("Deterministic mode").  Each takes the arguments of its plain form plus

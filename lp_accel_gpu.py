@@ -3,6 +3,10 @@ lp_accel_gpu.py), on HIP kernels.  One process on cuda:0; logs to stdout and <ou
 
     python lp_accel_gpu.py <eval.yaml>
 
+``loss_type: CE`` (softmax cross-entropy over the class indices of label column ``task``) takes the class count from the YAML key
+``num_classes`` when present, else from the largest train label, and logs the eight multiclass metrics of
+``metrics.multiclass_metrics``; the reference names the case but its label handling cannot run it.
+
 Deviation from the reference: the rank block ranks each modality's rows against the SAME split's fusion rows (row i of the
 fusion embeddings is row i's positive).  The reference's call site stacks the two splits' fusion rows, which fails for
 splits of different lengths, and passes the targets in the mask slot."""
@@ -49,11 +53,21 @@ def main():
 
     # the probe's plan is settled before any work, so that an unsupported loss fails fast
     n_all = s_train.shape[1] if (config.task == -1 and s_train.dim() > 1) else 1
-    plan = probe.plan(config, n_all)
+    n_classes = None
+    if config.loss_type == "CE" and config.task != -1:
+        # the class count: the YAML's num_classes (no default: the defaults are the reference's 19 keys), else the largest train label + 1
+        # when that column holds class indices; a column that does not gives no count, and the plan refuses CE as it always has
+        n_classes = config.get("num_classes")
+        col = s_train[:, config.task].double()
+        if n_classes is None and bool(((col >= 0) & (col == col.floor())).all()):
+            n_classes = int(col.max()) + 1
+    plan = probe.plan(config, n_all, n_classes)
     if config.task != -1:
         s_train, s_test = s_train[:, config.task], s_test[:, config.task]
     if plan is not None and plan["loss"] == "BCE":
         probe.check_binary_targets(s_train, s_test)
+    if plan is not None and plan["loss"] == "CE":
+        probe.check_class_targets(s_train, s_test, n_classes=plan["L"])
 
     if config.rank_metrics:
         ua, al = Uniformity(), Alignment()

@@ -10,8 +10,15 @@ contrastive weight is positive (multi-task).  The objective is
 A row is valid when the readout slot has something to read: a modality slot needs that modality present, the fusion slot (or a
 combination slot) any of its members (``readout_plan``).  Invalid rows get a prediction but no loss and no gradient.  The head
 keeps its own flat fp32 parameter / gradient / moment buffers (``probe.ProbeParams``) and its own AdamW launch; the clip uses ONE
-norm over trunk and head gradients together.  Not covered: capture as a hipGraph, data parallelism, the gradient-cached form, MLP
-heads, cross-entropy, EAO models.  INTEGRATION.md section I."""
+norm over trunk and head gradients together.
+
+``loss_type="CE"`` is softmax cross-entropy over ONE column of class indices (``task >= 0``) with a head of ``num_classes`` (2 .. 64)
+outputs, optional ``class_weights`` and ``label_smoothing``: its own kernel call (``mca_class_head_fwd_bwd``, csrc/class_head.hip) in
+the same place.  A negative label marks an unlabelled row: it gets a prediction and, with a positive contrastive weight, the
+contrastive gradient, but no task loss; the mean is torch's weighted mean over the labelled valid rows.
+
+Not covered: capture as a hipGraph, data parallelism, the gradient-cached form, MLP heads, probability (soft) targets, more than 64
+classes, CE over several label columns, EAO models.  INTEGRATION.md section I."""
 from __future__ import annotations
 
 import ctypes as C
@@ -24,10 +31,12 @@ from torch import nn
 from . import hip
 from .hip import call, ptr, stream_ptr
 from .optim import SQNORM_WORDS
-from .probe import LOSS_CODES, MAX_L, ProbeParams, check_binary_targets
+from .probe import CE, LOSS_CODES, MAX_L, ProbeParams, check_binary_targets, check_class_targets
 
 FINETUNE_DEFAULTS = {"loss_type": "MSE", "task": 0, "readout": "fusion", "head_lr": None, "task_weight": 1.0, "contrastive_weight": 0.0,
                      "head_warmup_steps": 0}
+# the keys of loss_type CE alone; finetune_settings returns them with a CE loss and refuses them with any other
+FINETUNE_CE_DEFAULTS = {"num_classes": None, "class_weights": None, "label_smoothing": 0.0}
 
 
 class TaskHead(nn.Module):
@@ -64,11 +73,20 @@ def finetune_settings(config) -> Dict[str, object]:
     given = config.get("finetune", None) or {}
     if not isinstance(given, dict):
         raise ValueError(f"finetune: must be a mapping, found {type(given).__name__}")
-    unknown = sorted(set(given) - set(FINETUNE_DEFAULTS))
+    unknown = sorted(set(given) - set(FINETUNE_DEFAULTS) - set(FINETUNE_CE_DEFAULTS))
     if unknown:
-        raise KeyError(f"finetune: unknown keys {unknown}; known: {sorted(FINETUNE_DEFAULTS)}")
+        raise KeyError(f"finetune: unknown keys {unknown}; known: {sorted(FINETUNE_DEFAULTS) + sorted(FINETUNE_CE_DEFAULTS)}")
     out = dict(FINETUNE_DEFAULTS)
     out.update(given)
+    if out["loss_type"] == CE:
+        for k, v in FINETUNE_CE_DEFAULTS.items():
+            out.setdefault(k, v)
+        out["num_classes"], out["class_weights"], out["label_smoothing"] = class_settings(out["num_classes"], out["class_weights"],
+                                                                                          out["label_smoothing"])
+    else:
+        stray = sorted(set(given) & set(FINETUNE_CE_DEFAULTS))
+        if stray:
+            raise ValueError(f"finetune: {stray} belong to loss_type CE, the loss is {out['loss_type']}")
     if isinstance(out["readout"], (list, tuple)):
         names = list((config.get("encoder_configs") or {}).keys())
         out["readout"] = frozenset(names.index(m) if m in names else int(m) for m in out["readout"])
@@ -76,6 +94,25 @@ def finetune_settings(config) -> Dict[str, object]:
     out["task_weight"], out["contrastive_weight"] = float(out["task_weight"]), float(out["contrastive_weight"])
     out["head_lr"] = None if out["head_lr"] is None else float(out["head_lr"])
     return out
+
+
+def class_settings(num_classes, class_weights, label_smoothing):
+    """(num_classes, class_weights or None, label_smoothing) of a CE head, validated: 2 .. 64 classes, num_classes finite
+    non-negative weights that are not all zero, a smoothing in [0, 1)"""
+    import math
+    if num_classes is None or isinstance(num_classes, bool) or int(num_classes) != num_classes or not 2 <= int(num_classes) <= MAX_L:
+        raise ValueError(f"loss_type CE needs num_classes in 2 .. {MAX_L}, found {num_classes!r}")
+    num_classes = int(num_classes)
+    if class_weights is not None:
+        class_weights = [float(v) for v in (class_weights.tolist() if isinstance(class_weights, torch.Tensor) else class_weights)]
+        if len(class_weights) != num_classes:
+            raise ValueError(f"class_weights has {len(class_weights)} entries for num_classes = {num_classes}")
+        if any(not math.isfinite(v) or v < 0 for v in class_weights) or not any(v > 0 for v in class_weights):
+            raise ValueError(f"class_weights must be finite, non-negative and not all zero, found {class_weights}")
+    label_smoothing = float(label_smoothing)
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1), found {label_smoothing}")
+    return num_classes, class_weights, label_smoothing
 
 
 def refuse_with(n_chunks: int, graph: bool):
@@ -87,7 +124,8 @@ def refuse_with(n_chunks: int, graph: bool):
 
 class FineTuneStep:
     def __init__(self, model, head: TaskHead, optimizer, readout="fusion", loss_type: str = "MSE", task: int = 0, task_weight: float = 1.0,
-                 contrastive_weight: float = 0.0, head_lr: Optional[float] = None, clip: float = 2.0, head_warmup_steps: int = 0, dp=None):
+                 contrastive_weight: float = 0.0, head_lr: Optional[float] = None, clip: float = 2.0, head_warmup_steps: int = 0, dp=None,
+                 num_classes: Optional[int] = None, class_weights=None, label_smoothing: float = 0.0):
         eng = model.engine
         if not eng.can_forward_backward():
             raise NotImplementedError("FineTuneStep needs native encoders: a torch encoder's backward runs under autograd "
@@ -104,8 +142,17 @@ class FineTuneStep:
             raise ValueError(f"the head reads {head.head.in_features} features, the pooled tokens have D = {eng.D}")
         if head.head.out_features > MAX_L:
             raise ValueError(f"n_outputs is {head.head.out_features}: the task-head kernel takes at most {MAX_L}")
-        if loss_type not in LOSS_CODES:
-            raise NotImplementedError(f"loss_type {loss_type!r}: the fine-tune step supports L1, MSE and BCE")
+        if loss_type == CE:
+            if head.head.out_features < 2:
+                raise NotImplementedError("a one-output head supports L1, MSE and BCE; CE needs a head of num_classes >= 2 outputs")
+            num_classes, class_weights, label_smoothing = class_settings(head.head.out_features if num_classes is None else num_classes,
+                                                                         class_weights, label_smoothing)
+            if head.head.out_features != num_classes:
+                raise ValueError(f"num_classes is {num_classes}, the head has {head.head.out_features} outputs")
+        elif loss_type not in LOSS_CODES:
+            raise NotImplementedError(f"loss_type {loss_type!r}: the fine-tune step supports L1, MSE and BCE (one column or several) and CE")
+        elif num_classes is not None or class_weights is not None or label_smoothing:
+            raise ValueError(f"num_classes, class_weights and label_smoothing belong to loss_type CE, the loss is {loss_type}")
         task_weight, contrastive_weight = float(task_weight), float(contrastive_weight)
         if task_weight < 0 or contrastive_weight < 0 or not (task_weight == task_weight and contrastive_weight == contrastive_weight):
             raise ValueError(f"task_weight = {task_weight} and contrastive_weight = {contrastive_weight} must not be negative")
@@ -114,11 +161,17 @@ class FineTuneStep:
         task = int(task)
         if task < -1:
             raise ValueError(f"task is {task}: a label column (>= 0) or -1 for all columns")
-        if task >= 0 and head.head.out_features != 1:
+        if loss_type == CE and task < 0:
+            raise ValueError("loss_type CE with task -1: CE reads one column of class indices (task >= 0)")
+        if loss_type != CE and task >= 0 and head.head.out_features != 1:
             raise ValueError(f"task = {task} selects one label column, the head has {head.head.out_features} outputs")
         self.model, self.head, self.opt = model, head, optimizer
         self.slot, self.any_bits = readout_plan(model, readout)
-        self.readout, self.loss_type, self.loss_code, self.task = readout, loss_type, LOSS_CODES[loss_type], task
+        self.readout, self.loss_type, self.loss_code, self.task = readout, loss_type, LOSS_CODES.get(loss_type), task
+        self.num_classes, self.label_smoothing = (num_classes, label_smoothing) if loss_type == CE else (None, 0.0)
+        self.class_weights = None          # (C,) fp32 on the device, or None for all ones
+        if loss_type == CE and class_weights is not None:
+            self.class_weights = torch.tensor(class_weights, dtype=torch.float32, device=eng.device)
         self.task_weight, self.contrastive_weight = task_weight, contrastive_weight
         self.head_lr = None if head_lr is None else float(head_lr)
         self.clip, self.head_warmup_steps = float(clip or 0.0), int(head_warmup_steps)
@@ -137,7 +190,7 @@ class FineTuneStep:
         """(fp32 device matrix, byte offset of the window's first column, its row stride): no copy of the columns"""
         y = labels.detach().to(device=self.model.engine.device, dtype=torch.float32)
         y = (y.reshape(-1, 1) if y.dim() < 2 else y.reshape(y.shape[0], -1)).contiguous()
-        if self.task >= 0:
+        if self.task >= 0:          # (CE too: its window is the one column of class indices)
             if self.task >= y.shape[1]:
                 raise IndexError(f"task = {self.task}: the labels have {y.shape[1]} columns")
             return y, 4 * self.task, y.shape[1]
@@ -146,7 +199,14 @@ class FineTuneStep:
         return y, 0, y.shape[1]
 
     def check_labels(self, *labels: torch.Tensor):
-        """before training: BCE targets must be 0 or 1 in the columns the head is trained on (probe.check_binary_targets)"""
+        """before training: BCE targets must be 0 or 1 in the columns the head is trained on (probe.check_binary_targets), CE targets
+        class indices below num_classes or negative for an unlabelled row (probe.check_class_targets)"""
+        if self.loss_type == CE:
+            cols = []
+            for y in labels:
+                y = y.reshape(-1, 1) if y.dim() < 2 else y.reshape(y.shape[0], -1)
+                cols.append(y[:, self.task])
+            check_class_targets(*cols, n_classes=self.num_classes, allow_unlabelled=True)
         if self.loss_type == "BCE":
             cols = []
             for y in labels:
@@ -155,7 +215,30 @@ class FineTuneStep:
             check_binary_targets(*cols)
 
     # ---- the kernel call -------------------------------------------------------------------------------------------------
+    def _class_kernel(self, pooled, present, b, y, y_off, ld, d_in, base):
+        """mca_class_head_fwd_bwd -> (logits (b, C), loss [mean CE, counted rows, W], d_pooled)"""
+        eng, dev = self.model.engine, self.model.engine.device
+        if b not in self._ws:
+            self._ws[b] = torch.empty(hip.lib().mca_class_head_workspace_bytes(b, self.L, self.D), dtype=torch.uint8, device=dev)
+        pred = torch.empty(b, self.L, dtype=torch.float32, device=dev)
+        loss = torch.empty(3, dtype=torch.float32, device=dev)
+        d_pooled = d_in if d_in is not None else torch.empty(b, eng.R, self.D, dtype=torch.float32, device=dev)
+        a = hip.ClassHeadArgs()
+        a.pooled, a.present, a.any_bits = ptr(pooled), ptr(present), self.any_bits
+        a.b, a.R, a.D, a.slot = b, eng.R, self.D, self.slot
+        a.w, a.bias, a.C = ptr(self.params.views[0]), ptr(self.params.views[1]), self.L
+        a.labels, a.ld_labels = y.data_ptr() + y_off, ld
+        a.class_weights, a.label_smoothing = ptr(self.class_weights), self.label_smoothing
+        a.task_weight, a.base_weight = self.task_weight, base
+        a.d_pooled_in, a.pred, a.loss, a.d_pooled = ptr(d_in), ptr(pred), ptr(loss), ptr(d_pooled)
+        a.gw, a.gb, a.accumulate = ptr(self.params.gviews[0]), ptr(self.params.gviews[1]), 0
+        a.workspace, a.workspace_bytes = ptr(self._ws[b]), self._ws[b].numel()
+        call("mca_class_head_fwd_bwd", C.byref(a), stream_ptr())
+        return pred, loss, d_pooled
+
     def _task_kernel(self, pooled, present, b, y, y_off, ld, d_in, base):
+        if self.loss_type == CE:
+            return self._class_kernel(pooled, present, b, y, y_off, ld, d_in, base)
         eng, dev = self.model.engine, self.model.engine.device
         if b not in self._ws:
             self._ws[b] = torch.empty(hip.lib().mca_task_head_workspace_bytes(b, self.L, self.D), dtype=torch.uint8, device=dev)
@@ -177,7 +260,8 @@ class FineTuneStep:
     # ---- one optimizer step ----------------------------------------------------------------------------------------------
     def step(self, batch, labels):
         """One optimizer step on a batch and its labels ((b,) or (b, columns)).  -> {"loss", "task_loss", "pred", "n_valid",
-        "modality_sample_mask"} (+ "contrastive_loss", "losses" with a positive contrastive weight, "modality_dropped" when drawn)."""
+        "modality_sample_mask"} (+ "contrastive_loss", "losses" with a positive contrastive weight, "modality_dropped" when drawn).
+        CE: "pred" holds the logits (b, C) and "n_valid" the counted rows (valid and labelled)."""
         m, eng = self.model, self.model.engine
         if len(eng._captured):
             raise RuntimeError("FineTuneStep.step: a GraphedStep of this engine is alive; delete it first")
@@ -272,4 +356,5 @@ class FineTuneStep:
         self.step_count = int(sd["step"])
 
 
-__all__ = ["TaskHead", "FineTuneStep", "readout_plan", "finetune_settings", "refuse_with", "FINETUNE_DEFAULTS"]
+__all__ = ["TaskHead", "FineTuneStep", "readout_plan", "finetune_settings", "class_settings", "refuse_with", "FINETUNE_DEFAULTS",
+           "FINETUNE_CE_DEFAULTS"]

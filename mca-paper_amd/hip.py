@@ -99,6 +99,21 @@ class TaskHeadArgs(C.Structure):
     ]
 
 
+class ClassHeadArgs(C.Structure):
+    """mca_class_head_args (include/mca_hip.h)"""
+    _fields_ = [
+        ("pooled", C.c_void_p), ("present", C.c_void_p), ("any_bits", C.c_uint32),
+        ("b", C.c_int), ("R", C.c_int), ("D", C.c_int), ("slot", C.c_int),
+        ("w", C.c_void_p), ("bias", C.c_void_p), ("C", C.c_int),
+        ("labels", C.c_void_p), ("ld_labels", C.c_int64),
+        ("class_weights", C.c_void_p), ("label_smoothing", C.c_float),
+        ("task_weight", C.c_float), ("base_weight", C.c_float),
+        ("d_pooled_in", C.c_void_p), ("pred", C.c_void_p), ("loss", C.c_void_p), ("d_pooled", C.c_void_p),
+        ("gw", C.c_void_p), ("gb", C.c_void_p), ("accumulate", C.c_int),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
 ATTN_Q_PRESCALED = 1
 ATTN_LAZY_REFERENCE = 2          # mca_attn_fwd: lazy softmax reference (include/mca_hip.h)
 
@@ -297,6 +312,9 @@ SIGNATURES = {
     "mca_probe_loss_accum": (_I, [_P, _I64, _I64, _P, _P]),
     "mca_task_head_workspace_bytes": (_I64, [_I, _I, _I]),
     "mca_task_head_fwd_bwd": (_I, [C.POINTER(TaskHeadArgs), _P]),
+    "mca_probe_head_ce_f32": (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _F, _P, _P]),
+    "mca_class_head_workspace_bytes": (_I64, [_I, _I, _I]),
+    "mca_class_head_fwd_bwd": (_I, [C.POINTER(ClassHeadArgs), _P]),
     # deterministic forms: the plain form's arguments + (scratch, scratch_floats) before the stream, and their size queries
     "mca_gemm_tn_acc_det_scratch": (_I64, [_I64, _I64, _I64]),
     "mca_gemm_tn_acc_det": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P, _I64, _P]),

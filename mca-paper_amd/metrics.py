@@ -322,7 +322,13 @@ def binary_metrics(probs: torch.Tensor, target: torch.Tensor) -> Dict[str, torch
            "accuracy": _safe_div(tp + tn, tp + tn + fp + fn), "f1": _safe_div(2 * tp, 2 * tp + fp + fn),
            "specificity": _safe_div(tn, tn + fp),
            "cm": torch.stack([torch.stack([tn, fp]), torch.stack([fn, tp])]).long()}
-    # exact curves: scores in descending order, one point per distinct score (the last index of each run of ties)
+    out["auroc"], out["auprc"], _, _ = _exact_curves(p, y)
+    return {k: (v if k == "cm" else v.float()) for k, v in out.items()}
+
+
+def _exact_curves(p: torch.Tensor, y: torch.Tensor):
+    """(auroc, auprc, positives, negatives) of fp64 scores p and 0/1 targets y, both 1-d: the exact curves, scores in descending
+    order, one point per distinct score (the last index of each run of ties); a zero division gives 0"""
     order = torch.argsort(p, descending=True, stable=True)
     ps, ys = p[order], y[order].double()
     n = ps.numel()
@@ -340,8 +346,48 @@ def binary_metrics(probs: torch.Tensor, target: torch.Tensor) -> Dict[str, torch
     P, N = tps[-1], fps[-1]
     lastf = last.double()
     area = ((fps - fp_prev) * (tps + tp_prev) * 0.5 * lastf).sum()
-    out["auroc"] = _safe_div(area, P * N)
-    out["auprc"] = _safe_div(((tps - tp_prev) * (tps / pos) * lastf).sum(), P)
+    return _safe_div(area, P * N), _safe_div(((tps - tp_prev) * (tps / pos) * lastf).sum(), P), P, N
+
+
+MULTICLASS_METRICS = BINARY_METRICS
+
+
+def multiclass_metrics(probs: torch.Tensor, target: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The eight ``task='multiclass'`` metrics the reference's CE branch names (lp_accel_gpu.py), from class probabilities
+    (n, C) and class-index targets (n,), as device tensor code.  The prediction is the argmax, a tie going to the LOWEST class
+    index; cm[true, pred] is (C, C) int64; accuracy is micro (trace / n); precision, recall, f1 and specificity are macro means
+    over the classes with tp + fp + fn > 0 (a zero division gives 0); auroc is the macro mean of the exact one-vs-rest AUROC
+    (``binary_metrics``' curve code) over the classes with at least one positive and one negative, 0 when there is none; auprc
+    the macro mean of the exact average precision over the classes with at least one positive.
+
+    These are torchmetrics' multiclass defaults as far as can be told without it: torchmetrics is not installed where this
+    was written, and the reference's CE branch cannot run (it takes the class count from the label width and hands
+    torchmetrics a target of the predictions' shape), so no reference numbers exist to pin these against."""
+    n, C = probs.shape
+    p = probs.double()
+    y = target.reshape(-1).long()
+    top = p.max(1, keepdim=True).values
+    classes = torch.arange(C, device=p.device)
+    pred = torch.where(p == top, classes[None, :], torch.full((1, 1), C, device=p.device)).min(1).values          # the lowest index among ties
+    pred = pred.clamp_max(C - 1)                                                                                  # (a row of NaN)
+    cm = torch.zeros(C * C, dtype=torch.long, device=p.device).scatter_add_(0, y * C + pred, torch.ones(n, dtype=torch.long, device=p.device))
+    cm = cm.view(C, C)
+    cmd = cm.double()
+    tp = cmd.diagonal()
+    fp, fn = cmd.sum(0) - tp, cmd.sum(1) - tp
+    tn = cmd.sum() - tp - fp - fn
+    seen = ((tp + fp + fn) > 0).double()
+    k = seen.sum()
+    macro = lambda v: _safe_div((v * seen).sum(), k)
+    out = {"precision": macro(_safe_div(tp, tp + fp)), "recall": macro(_safe_div(tp, tp + fn)), "accuracy": _safe_div(tp.sum(), cmd.sum()),
+           "cm": cm, "f1": macro(_safe_div(2 * tp, 2 * tp + fp + fn)), "specificity": macro(_safe_div(tn, tn + fp))}
+    roc, ap, has_roc, has_ap = [], [], [], []
+    for c in range(C):
+        a, r, P, N = _exact_curves(p[:, c].contiguous(), (y == c).long())
+        roc.append(a); ap.append(r); has_roc.append(((P > 0) & (N > 0)).double()); has_ap.append((P > 0).double())
+    roc, ap, has_roc, has_ap = torch.stack(roc), torch.stack(ap), torch.stack(has_roc), torch.stack(has_ap)
+    out["auroc"] = _safe_div((roc * has_roc).sum(), has_roc.sum())
+    out["auprc"] = _safe_div((ap * has_ap).sum(), has_ap.sum())
     return {k: (v if k == "cm" else v.float()) for k, v in out.items()}
 
 

@@ -7,6 +7,8 @@ the MLP ``Linear(D, H) -> Dropout -> ReLU -> Linear(H, L)`` is [W1, b1, W2, b2].
 the weight gradients as per-chunk partials added in a fixed order, the batch loss added to a device accumulator, then the
 existing ``mca_grad_sqnorm`` + ``mca_adamw_step`` (clip_grad_norm_ + AdamW with torch's defaults) reading the step's LR and
 bias corrections from a device table written once.  Nothing inside an epoch reads the device from the host.
+``loss_type="CE"`` (softmax cross-entropy over one column of class indices, a head of ``n_classes`` outputs) swaps the head kernel
+for ``mca_probe_head_ce_f32`` (csrc/class_head.hip) and the metrics for ``metrics.multiclass_metrics``; the rest of the step is shared.
 
 Host RNG: the permutations come from torch's own DataLoader over row indices (``EpochSampler``), drawn from the global CPU
 generator in the reference's order, and the initial weights are ``nn.Linear``'s own.  The dropout mask is a counter-based
@@ -23,6 +25,7 @@ from .hip import call, lib, ptr, stream_ptr
 from .optim import SQNORM_WORDS
 
 LOSS_CODES = {"L1": 0, "MSE": 1, "BCE": 2}
+CE = "CE"          # softmax cross-entropy over class-index labels: its own kernel (mca_probe_head_ce_f32), no code of the above
 MAX_D, MAX_L, MAX_H, MAX_B = 1024, 64, 1024, 4096
 
 
@@ -85,20 +88,25 @@ class Probe:
 
     def __init__(self, module: nn.Module, model_type: str, loss_type: str, x_train, y_train, x_eval, y_eval, batch_size: int,
                  lr: float, lr_at: Callable[[int], float], total_steps: int, clip: float, dropout: float, seed: int, device):
-        if loss_type not in LOSS_CODES:
-            raise NotImplementedError(f"loss_type {loss_type!r}: the probe supports L1, MSE and BCE")
+        if loss_type not in LOSS_CODES and loss_type != CE:
+            raise NotImplementedError(f"loss_type {loss_type!r}: the probe supports L1, MSE, BCE and CE")
         self.kind = "linear" if model_type == "linear" else "mlp"
-        self.loss_type, self.loss_code = loss_type, LOSS_CODES[loss_type]
+        self.loss_type, self.loss_code = loss_type, LOSS_CODES.get(loss_type)
         self.device = device
         self.x_train, self.x_eval = self._rows(x_train), self._rows(x_eval)
         self.y_train, self.y_eval = self._rows(y_train), self._rows(y_eval)
-        self.D, self.L = self.x_train.shape[1], self.y_train.shape[1]
         self.B = int(batch_size)
         self.params = ProbeParams(module, device)
+        # L is the head's width: the label columns, or for CE the classes (the module's outputs) over ONE column of class indices
+        self.D, self.L = self.x_train.shape[1], (self.params.views[-1].shape[0] if loss_type == CE else self.y_train.shape[1])
+        if loss_type == CE and (self.y_train.shape[1] != 1 or self.L < 2):
+            raise ValueError(f"CE probe: one column of class indices and a head of >= 2 classes, found {self.y_train.shape[1]} columns and "
+                             f"{self.L} outputs")
         self.H = self.params.views[0].shape[0] if self.kind == "mlp" else 0
         if self.D > MAX_D or self.L > MAX_L or self.H > MAX_H or self.B > MAX_B or self.B < 1:
             raise ValueError(f"probe sizes D={self.D} (<= {MAX_D}), L={self.L} (<= {MAX_L}), H={self.H} (<= {MAX_H}), "
                              f"batch {self.B} (1 .. {MAX_B}) out of range")
+        self.n_out = 1 if loss_type == CE else self.L          # loss elements a row: the mean's divisor is b * n_out
         self.clip, self.dropout, self.seed = float(clip), float(dropout), int(seed)
         self.n_train, self.n_eval = self.x_train.shape[0], self.x_eval.shape[0]
         self.steps_per_epoch = (self.n_train + self.B - 1) // self.B
@@ -139,7 +147,16 @@ class Probe:
         """the layer kernels of one batch of b rows; returns the number of loss partials written"""
         st = stream_ptr()
         v = self.params.views
-        if self.kind == "linear":
+        if self.loss_type == CE:
+            a, lda, aidx, k, w, bias, da, scale = x.data_ptr(), self.D, xidx, self.D, ptr(v[0]), ptr(v[1]), None, 0.0
+            if self.kind == "mlp":
+                call("mca_probe_nt_f32", x.data_ptr(), self.D, xidx, ptr(v[0]), self.D, ptr(v[1]), ptr(self.hid), self.H, b, self.H, self.D,
+                     2 if train else 1, self.dropout, self.seed & 0xFFFFFFFFFFFFFFFF, self.step, st)
+                scale = 1.0 / (1.0 - self.dropout) if self.dropout < 1.0 else 0.0
+                a, lda, aidx, k, w, bias, da = ptr(self.hid), self.H, None, self.H, ptr(v[2]), ptr(v[3]), ptr(self.dhid) if train else None
+            call("mca_probe_head_ce_f32", a, lda, aidx, k, w, bias, self.L, labels.data_ptr(), 1, yidx, b, pred,
+                 ptr(self.dz) if train else None, da, scale, ptr(self.part), st)
+        elif self.kind == "linear":
             call("mca_probe_head_f32", x.data_ptr(), self.D, xidx, self.D, ptr(v[0]), ptr(v[1]), self.L, labels.data_ptr(), yidx, b,
                  self.loss_code, pred, ptr(self.dz) if train else None, None, 0.0, ptr(self.part), st)
         else:
@@ -171,7 +188,7 @@ class Probe:
                      self.ws.numel(), ptr(g[2]), ptr(g[3]), st)
                 call("mca_probe_tn_f32", ptr(self.dhid), self.H, self.x_train.data_ptr(), self.D, rows, b, self.H, self.D, ptr(self.ws),
                      self.ws.numel(), ptr(g[0]), ptr(g[1]), st)
-            call("mca_probe_loss_accum", ptr(self.part), nb, b * self.L, ptr(self.acc), st)
+            call("mca_probe_loss_accum", ptr(self.part), nb, b * self.n_out, ptr(self.acc), st)
             self._optimizer_step()
 
     def _optimizer_step(self):
@@ -191,12 +208,14 @@ class Probe:
             r0 = s * self.B
             b = min(self.B, self.n_eval - r0)
             nb = self._forward(self.x_eval[r0:], None, self.y_eval[r0:], None, b, self.pred_eval.data_ptr() + 4 * r0 * self.L, False)
-            call("mca_probe_loss_accum", ptr(self.part), nb, b * self.L, self.acc.data_ptr() + 4, stream_ptr())
+            call("mca_probe_loss_accum", ptr(self.part), nb, b * self.n_out, self.acc.data_ptr() + 4, stream_ptr())
 
     # ---- the log record --------------------------------------------------------------------------------------------------
     def _metrics(self, pred, labels) -> Dict[str, torch.Tensor]:
         if self.loss_type == "BCE":
             return M.binary_metrics(M.binary_format(pred, self.B, self.L), labels)
+        if self.loss_type == CE:
+            return M.multiclass_metrics(torch.softmax(pred.double(), 1), labels.reshape(-1))
         return {"PCC": M.pearson(pred, labels)}
 
     def epoch_device_values(self) -> Dict[str, torch.Tensor]:
@@ -223,7 +242,8 @@ class Probe:
         for k, v in vals.items():
             n = v.numel()
             if k.endswith("_cm"):
-                out[k] = [[int(flat[o]), int(flat[o + 1])], [int(flat[o + 2]), int(flat[o + 3])]]
+                side = v.shape[0]          # (2, 2) binary, (C, C) multiclass
+                out[k] = [[int(flat[o + i * side + j]) for j in range(side)] for i in range(side)]
             else:
                 out[k] = flat[o]
             o += n
@@ -240,16 +260,38 @@ def check_binary_targets(*labels: torch.Tensor):
                              f"{' ...' if bad.numel() > 8 else ''} (binarise the labels first)")
 
 
-def plan(cfg, n_labels_all: Optional[int] = None) -> Optional[Dict[str, object]]:
+def check_class_targets(*labels: torch.Tensor, n_classes: int, allow_unlabelled: bool = False):
+    """CE targets must be class indices: integer values in [0, n_classes) (a negative value marks an unlabelled row where
+    ``allow_unlabelled``); raises before the first step, naming up to 8 offending values."""
+    for y in labels:
+        y = y.detach().reshape(-1).double()
+        bad = ~(y == y.floor()) | (y >= n_classes)          # (NaN is no integer)
+        if not allow_unlabelled:
+            bad |= y < 0
+        vals = torch.unique(y[bad])
+        if vals.numel():
+            raise ValueError(f"CE targets must be class indices 0 .. {n_classes - 1}"
+                             f"{' (or negative: unlabelled)' if allow_unlabelled else ''}, found {vals[:8].tolist()}"
+                             f"{' ...' if vals.numel() > 8 else ''}")
+
+
+def plan(cfg, n_labels_all: Optional[int] = None, n_classes: Optional[int] = None) -> Optional[Dict[str, object]]:
     """What the probe does for a config: None when only the rank block runs (model types other than linear / mlp), else
-    {model, loss, metrics, L} (L needs the labels' width when task == -1).  Raises NotImplementedError for CE and for L1 / MSE
-    with task == -1, whose metric (PCC) is 1-D."""
+    {model, loss, metrics, L} (L needs the labels' width when task == -1).  CE (softmax cross-entropy over ONE column of class
+    indices) is planned when the caller passes ``n_classes``, which becomes L; without it CE raises NotImplementedError, and with
+    task == -1 ValueError.  NotImplementedError also for L1 / MSE with task == -1, whose metric (PCC) is 1-D."""
     mt = cfg["model_type"]
     if not (mt == "linear" or mt.lower() == "mlp"):
         return None
     loss = cfg["loss_type"]
-    if loss == "CE":
-        raise NotImplementedError("loss_type CE: no probe YAML uses it")
+    if loss == CE:
+        if n_classes is None:
+            raise NotImplementedError("loss_type CE: needs the class count (plan(cfg, n_classes=...))")
+        if cfg["task"] == -1:
+            raise ValueError("loss_type CE with task -1: CE reads one column of class indices")
+        if not 2 <= int(n_classes) <= MAX_L:
+            raise ValueError(f"loss_type CE: {n_classes} classes, the head kernel takes 2 .. {MAX_L}")
+        return {"model": "linear" if mt == "linear" else "mlp", "loss": CE, "L": int(n_classes), "metrics": list(M.MULTICLASS_METRICS)}
     if loss not in LOSS_CODES:
         raise Exception("Didn't recognize config.metric")
     if loss in ("L1", "MSE") and cfg["task"] == -1:
@@ -271,4 +313,4 @@ def lr_schedule(name: str, lr: float, warmup: int, total: int) -> Callable[[int]
     return lambda step: lr_factor(name, step, warmup, total)
 
 
-__all__ = ["Probe", "ProbeParams", "EpochSampler", "build_module", "plan", "check_binary_targets", "lr_schedule"]
+__all__ = ["Probe", "ProbeParams", "EpochSampler", "build_module", "plan", "check_binary_targets", "check_class_targets", "lr_schedule"]
