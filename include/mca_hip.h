@@ -94,6 +94,14 @@ int mca_gemm_nt_res_lnbwd(const uint16_t* A, int64_t lda, const uint16_t* B, int
                           const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
                           float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16, float* dgamma,
                           int64_t M, int64_t N, int64_t K, mca_stream_t stream);
+/* The same call with the tile height chosen for the device: a workgroup owns 160 whole rows instead of 128 where that saves a
+ * round of workgroups over the CUs (rounds x rows per tile, ties to 128: M = 81,216 on 256 CUs is 508 tiles in two rounds instead
+ * of 635 in three), and the call above unchanged everywhere else.  Same arguments, same rules, same return codes in the same
+ * order; dx and dx_bf16 are the same bits from either tile, dgamma differs by the order of the atomic adds.              */
+int mca_gemm_nt_res_lnbwd_tall(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* residual, int64_t ldres,
+                               const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
+                               float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16, float* dgamma,
+                               int64_t M, int64_t N, int64_t K, mca_stream_t stream);
 
 /* C[N,K] += A[R,N]^T · B[R,K]   (weight gradient: reduction over the R token rows; fp32 atomics
  * into C, which the caller zeroes once per step).  lda/ldb % 8 == 0; N and K are arbitrary but the

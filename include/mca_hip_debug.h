@@ -27,7 +27,9 @@ extern "C" {
  *       each patch from global memory instead of staging strip rows through LDS (same results; profiles/patch_encoder.md).
  *       mca_patch_nd_ln_fwd: |c| caps the span the same way; it has no wavefront-per-patch form, the sign is ignored
  *   14  > 0: cap on the workgroups of the LayerNorm backward kernels (default 256) and of mca_reduce_rows (default 512)
- *   (13, in its earlier use, and 15 selected / tuned the forward attention forms of round 4; gone with tools/overlays/fwd64)
+ *   15  mca_gemm_nt_res_lnbwd_tall (and plan entry 7), the tile height: 1 = always 128 rows, 2 = always 160 rows; 0 = the height
+ *       rule of csrc/gemm_plan.h (mca_nt_rows_height).  mca_gemm_nt_res_lnbwd does not read it
+ *   (13 and 15, in their earlier use, selected / tuned the forward attention forms of round 4; gone with tools/overlays/fwd64)
  *   one-pass attention backward (attention_bwd1.hip), knob 9: 8 = s_memtime stamps (trace build, tools/trace_bwd1.py), 16 = launch
  *       order without the XCD remap, 64 = the plain (compiler-scheduled) kernel instead of the pipelined one (cross-check) */
 int mca_debug_set(int key, int value);
@@ -40,7 +42,10 @@ int mca_debug_reset(void);
  *   mca_dbg_plan_gemm_nt        entry 0 = mca_gemm_nt, 1 = _lnres, 2 = _geglu_fwd, 3 = _geglu_bwd (the last three read M, N = ip, K only;
  *                               kernel 0 from entry 2: the unfused pair mca_gemm_nt + mca_geglu_fwd),
  *                               4 = _geglu_fwd_saved, 5 = _geglu_bwd_saved (the plans of entries 2 and 3 with the saved kernel),
- *                               6 = _res_lnbwd (reads M, N, K only: the full-row kernel, one workgroup per 128 rows)
+ *                               6 = _res_lnbwd (reads M, N, K only: the full-row kernel, one workgroup per 128 rows),
+ *                               7 = _res_lnbwd_tall (reads M, N, K and cus, and knob 15: the plan of entry 6, or kernel 160 =
+ *                               gemm_nt_rows160_kernel with one workgroup per 160 rows where the height rule picks it; cus > 0
+ *                               touches no device: the engine asks with it before it chooses the entry point)
  *   mca_dbg_plan_gemm_tn        mca_gemm_tn_acc (its rule does not read the CU count)
  *   mca_dbg_plan_gemm_tn_group  mca_gemm_tn_acc_group over n members of N[i] x K[i]: grouped or single launches, and the row partition
  *   mca_dbg_gemm_kernel_name    the template instantiation a plan's `kernel` value stands for */

@@ -1064,6 +1064,211 @@ __global__ __launch_bounds__(512) void gemm_nt_rows_kernel(
   if (t != 0.f) atomicAdd(dgamma + tid, t);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The TALL form of the full-row kernel: 160 whole rows per workgroup (mca_gemm_nt_res_lnbwd_tall, where the height rule of
+// gemm_plan.h picks it: 81,216 rows are 508 tiles = two rounds on 256 CUs instead of 635 = three).  Same contract, same fp32 chains
+// (operands not swapped, k16-steps ascending), same row body; only the tile differs.  8 wavefronts as 1 (m) x 8 (n): wave w owns all
+// 160 rows x columns 64 w .. 64 w + 63 = 5 x 2 accumulators, so per k16-step it reads 5 A + 2 B fragments for 10 MFMAs.
+// Ring: three stages of (A image [160][32], B image [512][32]), 42 KiB each.  The B image is 4 loads per wave and stage as above;
+// the A image is 640 16-byte pieces = ten wave-loads, one per wave and a second one for waves 0 and 1 (pieces 512 .. 639, rows
+// 128 .. 159).  So waves 0 / 1 have SIX loads per stage in flight and waves 2 .. 7 FIVE, and every counted wait has two immediates
+// behind a wave-uniform branch (`six`).  vmcnt per wave, in issue order: S0 S1 S2 | S3 (middle of step 0) | S4 ...
+//   after the prologue 3 stages are outstanding (18 / 15 loads); S0 has landed once at most S1 + S2 are:  vmcnt(12) / vmcnt(10)
+//   in step kt, S(kt + 2) is the newest stage issued; S(kt + 1) has landed once at most S(kt + 2) is out:  vmcnt(6)  / vmcnt(5)
+//   in the last step but one nothing newer than S(kt + 1) exists:                                           vmcnt(0)
+// (vmcnt(5) would do for waves 0 / 1 too, one load late; vmcnt(6) on waves 2 .. 7 would let them pass with the newest load of
+// S(kt + 1) still in flight.)  Each wave waits for its own loads only; the barrier behind the wait completes the stage for everyone.
+// Epilogue: five passes, pass p = row block p: every wave writes its 64 columns x 32 rows (acc[p][0..1], all 16 registers) into cs
+// at row acc_row(r, lh); then wave w owns rows 4 w .. 4 w + 3 of the pass, two at a time, exactly as above.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(512) void gemm_nt_rows160_kernel(
+    const u16* __restrict__ A, int64_t lda, const u16* __restrict__ B, int64_t ldb, const float* residual, int64_t ldres,
+    const float* __restrict__ x, int64_t ldx, const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+    const float* __restrict__ gamma, float* dx, int64_t lddx, u16* __restrict__ dx_bf16, int64_t ld_bf16, float* __restrict__ dgamma,
+    int M, int K, int nwg) {
+  extern __shared__ __attribute__((aligned(16))) u16 lds2[];
+  constexpr unsigned STAGE_BYTES = ROWS160_STAGE * 2;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, lh = lane >> 5;
+  const bool six = __builtin_amdgcn_readfirstlane(wave) < 2;          // this wave carries a second A load (wave-uniform)
+  const int nkt = K / ROWS_BK;
+  const int m0 = xcd_remap(blockIdx.x, nwg) * ROWS160_BM;
+  const unsigned lds_base = lds_addr(lds2);
+
+  // fragment byte addresses inside a stage: row R (64-byte rows), k16-step ks: R * 64 + ((lh ^ sw(R)) << 4) ^ (32 * ks)
+  unsigned fa_addr[5], fb_addr[2];
+#pragma unroll
+  for (int i = 0; i < 5; i++) { const int r = i * 32 + l31; fa_addr[i] = lds_base + (unsigned)(r * 64 + ((lh ^ gl_sw<32>(r)) << 4)); }
+#pragma unroll
+  for (int j = 0; j < 2; j++) { const int r = wave * 64 + j * 32 + l31; fb_addr[j] = lds_base + (unsigned)(ROWS160_BM * 64) + (unsigned)(r * 64 + ((lh ^ gl_sw<32>(r)) << 4)); }
+
+  const u16* ga[2];          // pieces wave * 64 + lane (rows 0 .. 127) and, waves 0 / 1 only, 512 + wave * 64 + lane (rows 128 .. 159)
+  const u16* gb[4];
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    const int p = (i * 8 + (i ? wave & 1 : wave)) * 64 + lane, r = p >> 2, c = (p & 3) ^ gl_sw<32>(r);
+    int ra = m0 + r; if (ra > M - 1) ra = M - 1;          // rows past M: clamped (loaded and computed, never stored)
+    ga[i] = A + (int64_t)ra * lda + c * 8;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int p = (i * 8 + wave) * 64 + lane, r = p >> 2, c = (p & 3) ^ gl_sw<32>(r);          // r < 512 = N: no clamp
+    gb[i] = B + (int64_t)r * ldb + c * 8;
+  }
+  auto stage = [&](int k0, int st) {
+    u16* base = lds2 + st * ROWS160_STAGE;
+    lds_dma16(ga[0] + k0, base + wave * 512);
+    if (six) lds_dma16(ga[1] + k0, base + (8 + wave) * 512);
+#pragma unroll
+    for (int i = 0; i < 4; i++) lds_dma16(gb[i] + k0, base + ROWS160_BM * ROWS_BK + (i * 8 + wave) * 512);
+  };
+
+  f32x16 acc[5][2];
+#pragma unroll
+  for (int i = 0; i < 5; i++)
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+  stage(0, 0); stage(ROWS_BK, 1); stage(2 * ROWS_BK, 2);
+  u32x4v fa[2][5], fb[2][2];          // [k16-step][block]
+#define R160_RA(KS, I, SO) NT_DSREAD(fa[KS][I], (fa_addr[I] + (SO)) ^ (32u * (KS))); T256_SB
+#define R160_RB(KS, J, SO) NT_DSREAD(fb[KS][J], (fb_addr[J] + (SO)) ^ (32u * (KS))); T256_SB
+#define R160_MM(KS, I, J) acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&fa[KS][I]), \
+                                                                              *reinterpret_cast<const bf16x8*>(&fb[KS][J]), acc[I][J], 0, 0, 0); T256_SB
+// the software-pipelined k-step of gemm_tile.h (T256_GROUP_READING) for 5 x 2 blocks: the 10 MFMAs of k16-step KS with the 7 fragment
+// reads of k16-step KN in their gaps, one per gap; MID - the DMA of the stage three steps ahead - behind the first MFMA.  A block
+// is read again as late after its last MFMA of the group before as the order allows (the B blocks and A block 4 close a group).
+#define R160_FIRST_READS R160_RA(0, 0, 0u) R160_RB(0, 0, 0u) R160_RB(0, 1, 0u) R160_RA(0, 1, 0u) R160_RA(0, 2, 0u) R160_RA(0, 3, 0u) R160_RA(0, 4, 0u)
+#define R160_GROUP_READING(KS, KN, SO, MID)                                                                                       \
+  R160_MM(KS, 0, 0) MID R160_RA(KN, 0, SO) R160_MM(KS, 0, 1) R160_RA(KN, 1, SO) R160_MM(KS, 1, 0) R160_RA(KN, 2, SO)                \
+  R160_MM(KS, 1, 1) R160_RA(KN, 3, SO) R160_MM(KS, 2, 0) R160_RB(KN, 0, SO) R160_MM(KS, 2, 1) R160_RB(KN, 1, SO)                    \
+  R160_MM(KS, 3, 0) R160_RA(KN, 4, SO) R160_MM(KS, 3, 1) R160_MM(KS, 4, 0) R160_MM(KS, 4, 1)
+#define R160_GROUP(KS) R160_MM(KS, 0, 0) R160_MM(KS, 0, 1) R160_MM(KS, 1, 0) R160_MM(KS, 1, 1) R160_MM(KS, 2, 0) R160_MM(KS, 2, 1) \
+  R160_MM(KS, 3, 0) R160_MM(KS, 3, 1) R160_MM(KS, 4, 0) R160_MM(KS, 4, 1)
+  if (six) ps_wait_vm<12>(); else ps_wait_vm<10>();          // S0 has landed: at most S1 + S2 (6 / 5 loads each) are outstanding
+  __builtin_amdgcn_s_barrier();                              // ... for everyone
+  T256_SB
+  R160_FIRST_READS
+  int slot = 0;
+  for (int kt = 0; kt + 1 < nkt; kt++) {
+    const unsigned so = (unsigned)slot * STAGE_BYTES;
+    const int nxt = slot == 2 ? 0 : slot + 1;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); T256_SB
+    R160_GROUP_READING(0, 1, so, )
+    // stage kt + 1 has landed once only stage kt + 2 (6 loads of waves 0 / 1, 5 of the others) is outstanding; past the barrier
+    // every wave has read all of stage kt, whose slot takes stage kt + 3
+    if (kt + 2 < nkt) {
+      if (six) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
+    } else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    T256_SB
+    const unsigned son = (unsigned)nxt * STAGE_BYTES;
+    const bool fetch = kt + 3 < nkt;
+    R160_GROUP_READING(1, 0, son, if (fetch) stage((kt + 3) * ROWS_BK, slot); T256_SB)
+    slot = nxt;
+  }
+  {          // the last stage: nothing left to wait for or to fetch
+    const unsigned so = (unsigned)slot * STAGE_BYTES;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); T256_SB
+    R160_GROUP_READING(0, 1, so, )
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); T256_SB
+    R160_GROUP(1)
+  }
+#undef R160_RA
+#undef R160_RB
+#undef R160_MM
+#undef R160_FIRST_READS
+#undef R160_GROUP_READING
+#undef R160_GROUP
+  __syncthreads();                                   // every wave has read its last fragments: the ring is free
+
+  // ---------------- epilogue: acc[i][j][r] = C[m0 + i * 32 + acc_row(r, lh)][wave * 64 + j * 32 + l31] ----------------
+  float* cs = reinterpret_cast<float*>(lds2);        // [32][ROWS_CS_LD]
+  float4 gm[2], dg[2];
+#pragma unroll
+  for (int i = 0; i < 2; i++) { gm[i] = *reinterpret_cast<const float4*>(gamma + (lane + 64 * i) * 4); dg[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
+  const float inv_cols = 1.f / (float)ROWS_N;
+  // x, the residual, dx and its copy are streamed once: non-temporal, as in gemm_nt_rows_kernel
+  auto ld4 = [](const float* p) { const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)); return make_float4(t[0], t[1], t[2], t[3]); };
+  auto st4 = [](float* p, const float4& o) { __builtin_nontemporal_store(f32x4{o.x, o.y, o.z, o.w}, reinterpret_cast<f32x4*>(p)); };
+  auto st4b = [](u16* p, const float4& o) { const uint2 pk = ln_pack4bf(o); __builtin_nontemporal_store(u32x2v{pk.x, pk.y}, reinterpret_cast<u32x2v*>(p)); };
+#pragma unroll
+  for (int p = 0; p < 5; p++) {
+    // this wave's four rows of the pass, two pairs q of consecutive rows of C, their x and residual requested before the tile goes
+    // through LDS (rows past M clamped: loaded, never used; the in-place case: see gemm_nt_rows_kernel)
+    float4 xq[2][2][2], rq[2][2][2];          // [q][row a / b][i]
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      const int mrow = m0 + p * 32 + wave * 4 + q * 2;
+      const int64_t r0 = mrow < M ? mrow : M - 1, r1 = mrow + 1 < M ? mrow + 1 : r0;
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        const int c = (lane + 64 * i) * 4;
+        xq[q][0][i] = ld4(x + r0 * ldx + c); xq[q][1][i] = ld4(x + r1 * ldx + c);
+        if (residual) { rq[q][0][i] = ld4(residual + r0 * ldres + c); rq[q][1][i] = ld4(residual + r1 * ldres + c); }
+        else { rq[q][0][i] = make_float4(0.f, 0.f, 0.f, 0.f); rq[q][1][i] = make_float4(0.f, 0.f, 0.f, 0.f); }
+      }
+    }
+    if (p) __syncthreads();                          // the previous pass has been read
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+      for (int rr = 0; rr < 16; rr++) cs[acc_row(rr, lh) * ROWS_CS_LD + wave * 64 + j * 32 + l31] = acc[p][j][rr];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      const int lr = wave * 4 + q * 2;                // rows lr, lr + 1 of the pass
+      const int mrow = m0 + p * 32 + lr;
+      if (mrow >= M) continue;
+      const bool two = mrow + 1 < M;
+      const int64_t r0 = mrow, r1 = two ? r0 + 1 : r0;
+      const float* ca = cs + lr * ROWS_CS_LD;
+      const float* cb = cs + (two ? lr + 1 : lr) * ROWS_CS_LD;
+      float4 xa[2], xb[2], da[2], db[2];
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        const int c = (lane + 64 * i) * 4;
+        xa[i] = xq[q][0][i]; da[i] = *reinterpret_cast<const float4*>(ca + c);
+        xb[i] = xq[q][1][i]; db[i] = *reinterpret_cast<const float4*>(cb + c);
+      }
+      if (residual) {                                 // dy = A.B^T + residual, the add of the plain GEMM's epilogue
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+          const float4 ta = rq[q][0][i], tb = rq[q][1][i];
+          da[i].x += ta.x; da[i].y += ta.y; da[i].z += ta.z; da[i].w += ta.w;
+          db[i].x += tb.x; db[i].y += tb.y; db[i].z += tb.z; db[i].w += tb.w;
+        }
+      }
+      const float ma = mean_in[r0], ra = rstd_in[r0], mb = mean_in[r1], rb = rstd_in[r1];
+      float s1a, s2a, s1b, s2b;
+      ln_bwd_rows_stats<2>(xa, xb, da, db, gm, dg, ma, ra, mb, rb, two, inv_cols, s1a, s2a, s1b, s2b);
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        const int c = (lane + 64 * i) * 4;
+        float4 o = ln_bwd_row_dx(da[i], xa[i], ra, s1a, s2a);
+        st4(dx + r0 * lddx + c, o);
+        st4b(dx_bf16 + r0 * ld_bf16 + c, o);
+        if (two) {
+          o = ln_bwd_row_dx(db[i], xb[i], rb, s1b, s2b);
+          st4(dx + r1 * lddx + c, o);
+          st4b(dx_bf16 + r1 * ld_bf16 + c, o);
+        }
+      }
+    }
+  }
+  // block reduction of the dgamma partials through LDS, then one atomic per column and workgroup
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 2; i++) *reinterpret_cast<float4*>(cs + wave * ROWS_N + (lane + 64 * i) * 4) = dg[i];
+  __syncthreads();
+  float t = cs[tid];
+#pragma unroll
+  for (int w = 1; w < 8; w++) t += cs[w * ROWS_N + tid];
+  if (t != 0.f) atomicAdd(dgamma + tid, t);
+}
+
 // (the entry points of these kernels: end of file, after the weight-gradient kernels)
 
 // =====================================================================================================
@@ -1556,10 +1761,10 @@ extern "C" int mca_gemm_nt_lnres(const uint16_t* A, int64_t lda, const uint16_t*
 }
 
 // LayerNorm backward of dy = A·B^T (+ residual) in the epilogue of the full-row kernel: dy is never written (include/mca_hip.h).
-extern "C" int mca_gemm_nt_res_lnbwd(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* residual, int64_t ldres,
-                                     const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
-                                     float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16, float* dgamma,
-                                     int64_t M, int64_t N, int64_t K, mca_stream_t stream) {
+// (what both entry points refuse, in this order, before anything is planned or launched)
+static int res_lnbwd_refusal(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* residual, int64_t ldres,
+                             const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
+                             float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16, float* dgamma, int64_t M, int64_t N, int64_t K) {
   if (!A || !B || !x || !mean || !rstd || !gamma || !dx || !dx_bf16 || !dgamma || M <= 0 || N <= 0 || K <= 0) return MCA_E_BADARG;
   const int refusal = mca_nt_rows_refusal(M, N, K);
   if (refusal) return refusal;
@@ -1567,9 +1772,36 @@ extern "C" int mca_gemm_nt_res_lnbwd(const uint16_t* A, int64_t lda, const uint1
       (uintptr_t)x % 16 || (uintptr_t)gamma % 16 || (uintptr_t)dx % 16 || (uintptr_t)dx_bf16 % 16 || (uintptr_t)residual % 16)
     return MCA_E_ALIGN;
   if (lda < K || ldb < K || ldx < N || lddx < N || ld_bf16 < N || (residual && ldres < N)) return MCA_E_BADARG;
+  return MCA_OK;
+}
+extern "C" int mca_gemm_nt_res_lnbwd(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* residual, int64_t ldres,
+                                     const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
+                                     float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16, float* dgamma,
+                                     int64_t M, int64_t N, int64_t K, mca_stream_t stream) {
+  const int rc = res_lnbwd_refusal(A, lda, B, ldb, residual, ldres, x, ldx, mean, rstd, gamma, dx, lddx, dx_bf16, ld_bf16, dgamma, M, N, K);
+  if (rc != MCA_OK) return rc;
   const mca_gemm_plan p = mca_plan_gemm_nt_res_lnbwd(M);
   return launch_kernel<gemm_nt_rows_kernel>(p, stream, A, lda, B, ldb, residual, ldres, x, ldx, mean, rstd, gamma, dx, lddx, dx_bf16, ld_bf16,
                                                dgamma, (int)M, (int)K, p.nwg);
+}
+// The same with the tile height chosen for the device's CU count (mca_nt_rows_height): gemm_nt_rows160_kernel where 160-row tiles
+// save a round of workgroups, gemm_nt_rows_kernel and the plan above everywhere else.
+extern "C" int mca_gemm_nt_res_lnbwd_tall(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* residual, int64_t ldres,
+                                          const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
+                                          float* dx, int64_t lddx, uint16_t* dx_bf16, int64_t ld_bf16, float* dgamma,
+                                          int64_t M, int64_t N, int64_t K, mca_stream_t stream) {
+  const int rc = res_lnbwd_refusal(A, lda, B, ldb, residual, ldres, x, ldx, mean, rstd, gamma, dx, lddx, dx_bf16, ld_bf16, dgamma, M, N, K);
+  if (rc != MCA_OK) return rc;
+  const mca_gemm_plan p = mca_plan_gemm_nt_res_lnbwd_tall(M, mca_knobs, num_cus());
+  switch (p.kernel) {
+    case MCA_GK_NT_ROWS_LNBWD:
+      return launch_kernel<gemm_nt_rows_kernel>(p, stream, A, lda, B, ldb, residual, ldres, x, ldx, mean, rstd, gamma, dx, lddx, dx_bf16, ld_bf16,
+                                                   dgamma, (int)M, (int)K, p.nwg);
+    case MCA_GK_NT_ROWS160_LNBWD:
+      return launch_kernel<gemm_nt_rows160_kernel>(p, stream, A, lda, B, ldb, residual, ldres, x, ldx, mean, rstd, gamma, dx, lddx, dx_bf16,
+                                                      ld_bf16, dgamma, (int)M, (int)K, p.nwg);
+  }
+  return MCA_E_LAUNCH;
 }
 
 // dh = GEGLU'(h) applied to dg = A·B^T without materialising dg (fused epilogue).  A[M,K] (= d x_out, bf16), B[ip,K] (= W2^T
@@ -1769,6 +2001,10 @@ extern "C" int mca_dbg_plan_gemm_nt(int entry, const mca_nt_problem* pr, int cus
       if (pr->M <= 0 || pr->N <= 0 || pr->K <= 0) return MCA_E_BADARG;
       if (mca_nt_rows_refusal(pr->M, pr->N, pr->K)) return mca_nt_rows_refusal(pr->M, pr->N, pr->K);
       *out = mca_plan_gemm_nt_res_lnbwd(pr->M); return MCA_OK;
+    case 7:
+      if (pr->M <= 0 || pr->N <= 0 || pr->K <= 0) return MCA_E_BADARG;
+      if (mca_nt_rows_refusal(pr->M, pr->N, pr->K)) return mca_nt_rows_refusal(pr->M, pr->N, pr->K);
+      *out = mca_plan_gemm_nt_res_lnbwd_tall(pr->M, mca_knobs, cus); return MCA_OK;
   }
   return MCA_E_BADARG;
 }

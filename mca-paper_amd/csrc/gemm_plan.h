@@ -53,6 +53,8 @@ enum mca_gemm_kernel {
   // The full-row form (mca_gemm_nt_res_lnbwd): a workgroup owns whole rows of C and runs the LayerNorm backward's row body on
   // them.  Outside the counted table like the saved forms.
   MCA_GK_NT_ROWS_LNBWD = 128,                                                             // gemm_nt_rows_kernel
+  // ... and its 160-row sibling (mca_gemm_nt_res_lnbwd_tall, where the height rule below picks it)
+  MCA_GK_NT_ROWS160_LNBWD = 160,                                                          // gemm_nt_rows160_kernel
   // The column-blocked store (mca_gemm_nt_cb): the 256 x 256 bf16 kernel writing C as [N / 64][M][64].  Outside the counted table too.
   MCA_GK_NT_PERSIST256_CB = 256                                                           // gemm_nt_persist256_kernel<false,false,true>
 };
@@ -79,6 +81,7 @@ static inline const char* mca_gemm_kernel_name(int k) {
     case MCA_GK_NT_PERSIST_GEGLU_FWD_SAVED: return "gemm_nt_persist_kernel<6,false>";
     case MCA_GK_NT_PERSIST256_GEGLU_FWD_SAVED: return "gemm_nt_persist256_kernel<true,true>";
     case MCA_GK_NT_ROWS_LNBWD: return "gemm_nt_rows_kernel";
+    case MCA_GK_NT_ROWS160_LNBWD: return "gemm_nt_rows160_kernel";
     case MCA_GK_NT_PERSIST256_CB: return "gemm_nt_persist256_kernel<false,false,true>";
   }
   return k >= 0 && k < MCA_GK_COUNT ? names[k] : "?";
@@ -265,6 +268,38 @@ static inline mca_gemm_plan mca_plan_gemm_nt_res_lnbwd(int64_t M) {
   pl.kernel = MCA_GK_NT_ROWS_LNBWD;
   pl.n = ROWS_N; pl.tiles_n = 1; pl.nwg = (int)((M + ROWS_BM - 1) / ROWS_BM);
   pl.grid_x = pl.nwg; pl.grid_y = 1; pl.block = 512; pl.lds_bytes = ROWS_LDS_BYTES;
+  return pl;
+}
+
+// ---- the tall form (gemm_nt_rows160_kernel, mca_gemm_nt_res_lnbwd_tall): the same kernel with ROWS160_BM rows per workgroup, a ring
+// of three stages of (A image [160][32], B image [512][32]).  The epilogue's uses of the ring are those of the 128-row kernel.
+#define ROWS160_BM 160
+#define ROWS160_STAGE ((ROWS160_BM + ROWS_N) * ROWS_BK)          // elements per stage
+#define ROWS160_LDS_BYTES (ROWS_NSTAGE * ROWS160_STAGE * 2)      // 126 KiB
+#define MCA_KNOB_ROWS_HEIGHT 15                                  // 1 = always 128 rows, 2 = always 160 (include/mca_hip_debug.h)
+
+// The height rule.  Model: one workgroup per CU at a time (either form's LDS allows no second one), every round of the launch
+// lasts as long as one tile, and a tile's time follows its rows - the k-loop and the epilogue's streams alike.  A launch then
+// costs rounds x rows per tile = ceil(ceil(M / h) / cus) * h row times on its busiest CU.  Ties go to 128, the form with the
+// smaller tail.
+static inline int64_t mca_nt_rows_cost(int64_t M, int h, int cus) {
+  const int64_t tiles = (M + h - 1) / h;
+  return (tiles + cus - 1) / cus * h;
+}
+static inline int mca_nt_rows_height(int64_t M, int cus) {
+  if (cus < 1) cus = 1;
+  return mca_nt_rows_cost(M, ROWS160_BM, cus) < mca_nt_rows_cost(M, ROWS_BM, cus) ? ROWS160_BM : ROWS_BM;
+}
+// mca_gemm_nt_res_lnbwd_tall: the plan of mca_gemm_nt_res_lnbwd where the height is 128, one workgroup per 160 rows otherwise.
+// Refusals: mca_nt_rows_refusal.
+static inline mca_gemm_plan mca_plan_gemm_nt_res_lnbwd_tall(int64_t M, const int* knobs, int cus) {
+  const int forced = knobs[MCA_KNOB_ROWS_HEIGHT];
+  const int h = forced == 1 ? ROWS_BM : forced == 2 ? ROWS160_BM : mca_nt_rows_height(M, cus);
+  if (h == ROWS_BM) return mca_plan_gemm_nt_res_lnbwd(M);
+  mca_gemm_plan pl = {};
+  pl.kernel = MCA_GK_NT_ROWS160_LNBWD;
+  pl.n = ROWS_N; pl.tiles_n = 1; pl.nwg = (int)((M + ROWS160_BM - 1) / ROWS160_BM);
+  pl.grid_x = pl.nwg; pl.grid_y = 1; pl.block = 512; pl.lds_bytes = ROWS160_LDS_BYTES;
   return pl;
 }
 

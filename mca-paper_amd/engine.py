@@ -53,11 +53,13 @@ def debug_options() -> dict:
     the weight-gradient, LayerNorm-backward, row-reduction and table-gradient launches: FusionEngine.set_deterministic),
     geglu_saved=0 (the FF1 GEMM keeps h = [a | gate] and the backward evaluates gelu again, instead of the saved factors:
     FusionEngine.geglu_saved_factors), ln_rows=0 (the trunk LayerNorm backward as a launch of its own behind the data-gradient
-    GEMM instead of in that GEMM's full-row epilogue: FusionEngine.fuse_ln_rows), qkv_hm=0 (q | k | v and dO always as row-major
+    GEMM instead of in that GEMM's full-row epilogue: FusionEngine.fuse_ln_rows), ln_rows_tall=0 (that fused launch always with
+    128-row tiles, mca_gemm_nt_res_lnbwd, instead of 160-row tiles where they save a round of workgroups:
+    FusionEngine.ln_rows_tall), qkv_hm=0 (q | k | v and dO always as row-major
     matrices, with the one-pass backward's packed copies, instead of head-major from their GEMMs: FusionEngine.qkv_head_major).
     Kernel-level knobs: include/mca_hip_debug.h (hip.knobs)."""
     opts = {"overlap_wgrad": None, "group_wgrad": True, "mask_mfma": True, "dkv_keys": 128, "lazy_softmax": True,
-            "onepass": None, "deterministic": False, "geglu_saved": True, "ln_rows": True,
+            "onepass": None, "deterministic": False, "geglu_saved": True, "ln_rows": True, "ln_rows_tall": True,
             "qkv_hm": True}          # onepass=0|1: the one-pass attention backward (attention_bwd1.hip); default: by size
     for item in filter(None, os.environ.get("MCA_DEBUG", "").split(",")):
         k, _, v = item.partition("=")
@@ -133,6 +135,8 @@ class FusionEngine:
         # The trunk LayerNorm backward inside the data-gradient GEMM that produces its dy (mca_gemm_nt_res_lnbwd: a workgroup owns
         # whole rows, dy never reaches memory).  Where it applies: ln_rows_backward.
         self.fuse_ln_rows = bool(self.dbg["ln_rows"])
+        # ... through the entry point that picks 160-row tiles where they save a round of workgroups: ln_rows_tall_form.
+        self.ln_rows_tall = bool(self.dbg["ln_rows_tall"])
         # q | k | v and dO written head-major by their GEMMs (mca_gemm_nt_cb) and read in place by the attention kernels, where the
         # one-pass backward runs: qkv_head_major decides once per forward.  rows_only: a forward whose q | k are read afterwards
         # by code that takes row-major matrices only (the attention readout) keeps the row-major layout.
@@ -453,6 +457,7 @@ class FusionEngine:
         bf = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
         u8 = lambda *s: torch.empty(*s, dtype=torch.uint8, device=dev)
         ws = dict(b=b, T=T, gen=0)
+        ws["ln_rows_tall"] = {}          # K -> the fused LayerNorm-backward GEMM of (T, D, K) takes the 160-row entry point (ln_rows_tall_form)
         ws["x"] = [f32(T, D) for _ in range(self.L + 1)]
         ws["layers"] = [dict(x1=f32(T, D), m1=f32(T), r1=f32(T), m2=f32(T), r2=f32(T), xn_b=bf(T, D), qkv=bf(T, 3 * D),
                              o=bf(T, D), lse=f32(b, H, N), x1n_b=bf(T, D), h=bf(T, 2 * Ip), g=bf(T, Ip),
@@ -800,13 +805,29 @@ class FusionEngine:
         data-gradient shapes of the step (K = 2 Ip, 3 D, 2 D) take it: profiles/ln_rows_fusion.md has each against its pair."""
         return self.fuse_ln_rows and self.ln_in_gemm(T) and self.D == 512 and not self._deterministic and not self.eao
 
-    def _gemm_ln_bwd(self, A, B, K, residual, x, gamma, mean, rstd, dgamma, dx, dx_bf16, T):
+    def ln_rows_tall_form(self, ws, K: int) -> bool:
+        """Whether the fused launch of this workspace's (T, D, K) shape goes to mca_gemm_nt_res_lnbwd_tall: where that entry point's
+        plan for this device's CU count is the 160-row kernel (csrc/gemm_plan.h, mca_nt_rows_height: T = 81,216 and 40,608 on 256
+        CUs; never b = 2 or b = 8), and unless MCA_DEBUG=ln_rows_tall=0.  The plan is asked once per workspace and shape, with the
+        CU count given, so no device is touched."""
+        if not self.ln_rows_tall:
+            return False
+        tall = ws["ln_rows_tall"]
+        if K not in tall:
+            pl = hip.GemmPlan()
+            cus = torch.cuda.get_device_properties(self.device).multi_processor_count
+            rc = hip.lib().mca_dbg_plan_gemm_nt(hip.PLAN_RES_LNBWD_TALL, C.byref(hip.NtProblem(M=ws["T"], N=self.D, K=K)), cus, C.byref(pl))
+            tall[K] = rc == 0 and pl.kernel == hip.GK_NT_ROWS160_LNBWD
+        return tall[K]
+
+    def _gemm_ln_bwd(self, A, B, K, residual, x, gamma, mean, rstd, dgamma, dx, dx_bf16, ws):
         """dx (fp32, may be the residual), dx_bf16, dgamma += : the LayerNorm backward of dy = A B^T (+ residual) in one launch; timed
-        under the row of the GEMM it replaces"""
-        D = self.D
+        under the row of the GEMM it replaces, whichever tile height runs (ln_rows_tall_form)"""
+        D, T = self.D, ws["T"]
         if hip.PROFILE is not None:
             hip.set_tag(f"{T}x{D}x{K} f32{' +res' if residual is not None else ''}")
-        call("mca_gemm_nt_res_lnbwd", ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(residual), residual.stride(0) if residual is not None else 0,
+        call("mca_gemm_nt_res_lnbwd_tall" if self.ln_rows_tall_form(ws, K) else "mca_gemm_nt_res_lnbwd",
+             ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(residual), residual.stride(0) if residual is not None else 0,
              ptr(x), x.stride(0), ptr(mean), ptr(rstd), ptr(gamma), ptr(dx), dx.stride(0), ptr(dx_bf16), dx_bf16.stride(0), ptr(dgamma),
              T, D, K, stream_ptr(), flops=2.0 * T * D * K, profile_as="mca_gemm_nt")
         if hip.PROFILE is not None:
@@ -1044,7 +1065,7 @@ class FusionEngine:
         top = ws["layers"][self.L - 1]["dxo_b"] if self.L else ws["dx_b"]
         if self.ln_rows_backward(T):
             self._gemm_ln_bwd(ws["dkvp"], self.wp["kvT"], 2 * D, None, ws["x"][self.L], m.norm.gamma, ws["mf"], ws["rf"], G(m.norm.gamma),
-                              dx_other, top, T)
+                              dx_other, top, ws)
         else:
             self.gemm_nt(ws["dkvp"], self.wp["kvT"], dx, T, D, 2 * D)                    # d (final-normed tokens), fp32
             self._ln_bwd(ws, dx, D, ws["x"][self.L], m.norm.gamma, ws["mf"], ws["rf"], T, D, G(m.norm.gamma), dx=dx_other, dx_bf16=top)
@@ -1097,7 +1118,7 @@ class FusionEngine:
                 on_side(lambda dh=dh, a=a, gw1=gw1: (tn(dh, a["x1n_b"], gw1, T, I, D), tn(dh[:, Ip:], a["x1n_b"], gw1[I:], T, I, D)))
             rows = self.ln_rows_backward(T)          # d x1n / d xn stay in the GEMM's tile; dx is read (residual) and written in place
             if rows:
-                self._gemm_ln_bwd(dh, w["w1T"], 2 * Ip, dx, a["x1"], g, a["m2"], a["r2"], G(g), dx, dx1, T)
+                self._gemm_ln_bwd(dh, w["w1T"], 2 * Ip, dx, a["x1"], g, a["m2"], a["r2"], G(g), dx, dx1, ws)
             else:
                 self.gemm_nt(dh, w["w1T"], dx_other, T, D, 2 * Ip, residual=dx)            # d x1n = dh @ W1 + dx
                 self._ln_bwd(ws, dx_other, D, a["x1"], g, a["m2"], a["r2"], T, D, G(g), dx=dx, dx_bf16=dx1)   # dx = d x1
@@ -1121,7 +1142,7 @@ class FusionEngine:
             else:
                 on_side(lambda dqkv=dqkv, a=a, gq=gq: tn(dqkv, a["xn_b"], gq, T, 3 * D, D))
             if rows:
-                self._gemm_ln_bwd(dqkv, w["qkvT"], 3 * D, dx, ws["x"][i], g, a["m1"], a["r1"], G(g), dx, below, T)
+                self._gemm_ln_bwd(dqkv, w["qkvT"], 3 * D, dx, ws["x"][i], g, a["m1"], a["r1"], G(g), dx, below, ws)
             else:
                 self.gemm_nt(dqkv, w["qkvT"], dx_other, T, D, 3 * D, residual=dx)          # d xn = dqkv @ Wqkv + d x1
                 self._ln_bwd(ws, dx_other, D, ws["x"][i], g, a["m1"], a["r1"], T, D, G(g), dx=dx, dx_bf16=below)  # dx = d x_in

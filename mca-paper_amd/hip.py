@@ -199,6 +199,9 @@ PLAN_NT, PLAN_LNRES, PLAN_GEGLU_FWD, PLAN_GEGLU_BWD, PLAN_GEGLU_FWD_SAVED, PLAN_
 GK_SAVED = 64          # csrc/gemm_plan.h MCA_GK_SAVED: a saved-factor kernel's value is its unsaved sibling's + this
 PLAN_RES_LNBWD = 6     # mca_gemm_nt_res_lnbwd
 GK_NT_ROWS_LNBWD = 128          # csrc/gemm_plan.h MCA_GK_NT_ROWS_LNBWD: gemm_nt_rows_kernel
+PLAN_RES_LNBWD_TALL = 7         # mca_gemm_nt_res_lnbwd_tall
+GK_NT_ROWS160_LNBWD = 160       # csrc/gemm_plan.h MCA_GK_NT_ROWS160_LNBWD: gemm_nt_rows160_kernel
+KNOB_ROWS_HEIGHT = 15           # csrc/gemm_plan.h MCA_KNOB_ROWS_HEIGHT: 1 = always 128 rows, 2 = always 160 (the tall entry point only)
 GK_NT_PERSIST256_CB = 256       # csrc/gemm_plan.h MCA_GK_NT_PERSIST256_CB: the 256 x 256 kernel with the column-blocked store (mca_gemm_nt_cb)
 
 
@@ -246,6 +249,7 @@ SIGNATURES = {
     "mca_gemm_nt_geglu_bwd_saved": (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P]),
     # full-row GEMM + LayerNorm backward: A, lda, B, ldb, residual, ldres, x, ldx, mean, rstd, gamma, dx, lddx, dx_bf16, ld_bf16, dgamma, M, N, K
     "mca_gemm_nt_res_lnbwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P]),
+    "mca_gemm_nt_res_lnbwd_tall": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P]),
     "mca_geglu_fwd_saved": (_I, [_P, _P, _I64, _I, _P]),
     "mca_geglu_bwd_saved": (_I, [_P, _P, _P, _I64, _I, _P]),
     "mca_gemm_tn_acc": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
